@@ -8,7 +8,7 @@
 #   tests                      pytest -m gpu, the whole suite
 #   tests:<f1>,<f2>            just those test files (verbose, fail fast)
 #   smoke                      __graft_entry__.smoke()
-#   bench[:<workload>[:<args>]]  python bench.py --workload <workload> <args>; args use ',' for
+#   bench[:<workload>[:<args>]]  python bench.py --full --workload <workload> <args>; args use ',' for
 #                              spaces (bench:q6:--steps,20), leading VAR=value args go to its
 #                              environment (bench:q6:CUBIT_BENCH_PARTITION=0/8,--steps,20) — default:
 #                              the driver's N = 1 line
@@ -17,7 +17,7 @@
 #   dist1                      the bench as one torchrun rank over RCCL (the N > 1 code path)
 #   dist2                      two gloo ranks sharing the GPU (strong scaling rehearsal)
 #   distg:<n>                  n gloo ranks sharing the GPU (n <= 4 here: the N = 8 case is the driver's)
-#   self:<n>[:<args>]          plain `python bench.py --gpus n` with no launcher (bench.py starts its own
+#   self:<n>[:<args>]          plain `python bench.py --full --gpus n` with no launcher (bench.py starts its own
 #                              n ranks), gloo, every rank on the one GPU (CUBIT_BENCH_SHARE_GPU=1)
 #   apitrace[:<sf>,<tasks>]    HIP API + kernel + copy trace of examples/q6_scan (default 100 8), then
 #                              scripts/api_timeline.py over runs 0..3 into $OUT/apitrace_runs.txt
@@ -60,37 +60,37 @@ for step in "$@"; do
       envs=(); args=()
       for x in ${a//,/ }; do [[ $x == *=* && $x != --* ]] && envs+=("$x") || args+=("$x"); done
       if [ -n "$w" ]; then
-        env "${envs[@]}" timeout -k 10 600 python bench.py --workload "$w" "${args[@]}" > "$OUT/$n.bench_$w.json" 2> "$log"
+        env "${envs[@]}" timeout -k 10 600 python bench.py --full --workload "$w" "${args[@]}" > "$OUT/$n.bench_$w.json" 2> "$log"
       else
-        timeout -k 10 600 python bench.py > "$OUT/$n.bench.json" 2> "$log"
+        timeout -k 10 600 python bench.py --full > "$OUT/$n.bench.json" 2> "$log"
       fi ;;
     profile)
       w=${rest%%:*}; a=${rest#*:}; [ "$a" = "$rest" ] && a=""
       d=$OUT/prof/$w
       mkdir -p "$d"
       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$d/kt" -o kt -- \
-          python3 bench.py --workload "$w" --steps 20 --warmup 5 --no-cpu-baseline ${a//,/ } > "$d/bench_kt.log" 2>&1 &&
+          python3 bench.py --full --workload "$w" --steps 20 --warmup 5 --no-cpu-baseline ${a//,/ } > "$d/bench_kt.log" 2>&1 &&
       timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$d/fetch" -o fetch -- \
-          python3 bench.py --workload "$w" --steps 20 --warmup 5 --no-cpu-baseline ${a//,/ } > "$d/bench_fetch.log" 2>&1 &&
+          python3 bench.py --full --workload "$w" --steps 20 --warmup 5 --no-cpu-baseline ${a//,/ } > "$d/bench_fetch.log" 2>&1 &&
       timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$d/write" -o write -- \
-          python3 bench.py --workload "$w" --steps 20 --warmup 5 --no-cpu-baseline ${a//,/ } > "$d/bench_write.log" 2>&1 ;;
+          python3 bench.py --full --workload "$w" --steps 20 --warmup 5 --no-cpu-baseline ${a//,/ } > "$d/bench_write.log" 2>&1 ;;
     dist1)
       CUBIT_BENCH_DIST1=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-          --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline \
+          --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline \
           --no-maintenance --no-zonemap-leg > "$OUT/$n.bench_dist1_rccl.json" 2> "$log" ;;
     dist2)
       CUBIT_BENCH_SHARE_GPU=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-          --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 2 --steps 10 --warmup 3 --dist-backend gloo \
+          --master-addr 127.0.0.1 --master-port 29518 bench.py --full --gpus 2 --steps 10 --warmup 3 --dist-backend gloo \
           --no-cpu-baseline > "$OUT/$n.bench_dist2_gloo.json" 2> "$log" ;;
     distg)
       [ "$rest" -ge 2 ] && [ "$rest" -le 4 ] || { echo "distg: 2 to 4 ranks" >&2; exit 2; }
       CUBIT_BENCH_SHARE_GPU=1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$rest" \
-          --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus "$rest" --steps 10 --warmup 3 --dist-backend gloo \
+          --master-addr 127.0.0.1 --master-port 29519 bench.py --full --gpus "$rest" --steps 10 --warmup 3 --dist-backend gloo \
           --no-cpu-baseline > "$OUT/$n.bench_dist${rest}_gloo.json" 2> "$log" ;;
     self)
       nn=${rest%%:*}; a=${rest#*:}; [ "$a" = "$rest" ] && a=""
       [ "$nn" -ge 2 ] && [ "$nn" -le 4 ] || { echo "self: 2 to 4 ranks" >&2; exit 2; }
-      CUBIT_BENCH_SHARE_GPU=1 timeout -k 10 500 python bench.py --gpus "$nn" --steps 10 --warmup 3 \
+      CUBIT_BENCH_SHARE_GPU=1 timeout -k 10 500 python bench.py --full --gpus "$nn" --steps 10 --warmup 3 \
           --dist-backend gloo --no-cpu-baseline ${a//,/ } > "$OUT/$n.bench_self${nn}_gloo.json" 2> "$log" ;;
     apitrace)
       a=${rest:-100,8}

@@ -75,6 +75,33 @@ def test_bench_refuses_a_launcher_world_size_other_than_gpus():
     assert r.stdout == ""
 
 
+def test_dump_outputs_writes_float64_and_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: count, row ids and tile counts as float64 .npy; more row ids than
+    DUMP_MAX_IDS are cut to the same ascending sample on every call."""
+    import numpy as np
+
+    assert bench.DUMP_MAX_IDS * 8 <= 32 * 2 ** 20  # half of the 64 MB a dump may take
+    ids = np.arange(7, 7 + 3 * 1000, 3, dtype=np.int64) + (1 << 40)  # exact in float64
+    tiles = np.array([400, 0, 600], dtype=np.uint64)
+    bench.dump_outputs(tmp_path / "a", ids, tiles)
+    got = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["count.npy", "row_ids.npy", "tile_counts.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["count.npy"].tolist() == [1000.0]
+    assert np.array_equal(got["row_ids.npy"].astype(np.int64), ids)
+    assert got["tile_counts.npy"].tolist() == [400.0, 0.0, 600.0]
+    monkeypatch.setattr(bench, "DUMP_MAX_IDS", 100)
+    bench.dump_outputs(tmp_path / "b", ids, None, "_rank1")
+    bench.dump_outputs(tmp_path / "c", ids, None, "_rank1")
+    bench.dump_outputs(tmp_path / "d", ids, None, share=4)
+    assert len(np.load(tmp_path / "d" / "row_ids.npy")) == 25  # four ranks share the budget
+    b, c = np.load(tmp_path / "b" / "row_ids_rank1.npy"), np.load(tmp_path / "c" / "row_ids_rank1.npy")
+    assert sorted(p.name for p in (tmp_path / "b").iterdir()) == ["count_rank1.npy", "row_ids_rank1.npy"]
+    assert np.load(tmp_path / "b" / "count_rank1.npy").tolist() == [1000.0]  # the count stays the whole output's
+    assert len(b) == 100 and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and np.isin(b.astype(np.int64), ids).all()
+
+
 def test_cpu_baseline_times_the_whole_partition(li001, monkeypatch):
     """bench.cpu_baseline over a whole partition: the box's CPU share of threads,
     the 1-thread point, and the count / Σ row id checked against the scan it is compared with."""
