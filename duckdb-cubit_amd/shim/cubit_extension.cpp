@@ -67,6 +67,7 @@
 
 #include "cubit_gpu.h"
 #include "cubit_scan.h"
+#include "cubit_shim_core.hpp"
 
 #include <memory>
 #include <mutex>
@@ -237,40 +238,51 @@ static void Check(int rc) {
     }
 }
 
-// ------------------------------------------------------------------ filters
+// ------------------------------------------------------------------ types
 
-// Physical types whose values the GPU compares exactly, carried as int64: the signed integers up
-// to 64 bits (DATE, TIME, TIMESTAMP*, DECIMAL(≤18) included), BOOLEAN, the unsigned integers up to
-// 32 bits, and FLOAT / DOUBLE as their bit patterns (the library compares them with DuckDB's
-// floating-point operators, include/cubit_gpu.h), UBIGINT as its bits (compared unsigned), and
-// VARCHAR as int32 codes of the table's order-preserving dictionary (constants cross as
-// cubit_strings), and HUGEINT / UHUGEINT as codes of a dictionary over their 16-byte order keys
-// (cubit_key128: the codes are the values' ranks; constants cross as cubit_strings over keys).
-static bool GpuPhysical(PhysicalType t) {
+// Everything that needs no DuckDB object — the type table, value conversion, segment images,
+// partition arithmetic, index-spec text — is cubit_shim_core.hpp's.
+namespace core = cubit_shim;
+using core::RowValid;
+
+// The one switch over PhysicalType that classifies a type: what the GPU holds each as, and
+// everything else the shim asks about it, is core::TraitsOf's table.
+static core::Phys PhysOf(PhysicalType t) {
     switch (t) {
     case PhysicalType::BOOL:
+        return core::Phys::Bool;
     case PhysicalType::INT8:
+        return core::Phys::I8;
     case PhysicalType::INT16:
+        return core::Phys::I16;
     case PhysicalType::INT32:
+        return core::Phys::I32;
     case PhysicalType::INT64:
+        return core::Phys::I64;
     case PhysicalType::UINT8:
+        return core::Phys::U8;
     case PhysicalType::UINT16:
+        return core::Phys::U16;
     case PhysicalType::UINT32:
-    case PhysicalType::UINT64:   // the bits, compared unsigned
+        return core::Phys::U32;
+    case PhysicalType::UINT64:
+        return core::Phys::U64;
     case PhysicalType::FLOAT:
+        return core::Phys::F32;
     case PhysicalType::DOUBLE:
-    case PhysicalType::VARCHAR:  // as codes of an order-preserving dictionary (cubit_dict)
-    case PhysicalType::INT128:   // as codes of a dictionary over the values' order keys
+        return core::Phys::F64;
+    case PhysicalType::VARCHAR:
+        return core::Phys::Varchar;
+    case PhysicalType::INT128:
+        return core::Phys::I128;
     case PhysicalType::UINT128:
-        return true;
+        return core::Phys::U128;
     default:
-        return false;
+        return core::Phys::Unsupported;
     }
 }
-
-// a column held as dictionary codes: VARCHAR (the strings), HUGEINT / UHUGEINT (their order keys)
-static bool DictPhysical(PhysicalType t) {
-    return t == PhysicalType::VARCHAR || t == PhysicalType::INT128 || t == PhysicalType::UINT128;
+static core::PhysTraits Traits(PhysicalType t) {
+    return core::TraitsOf(PhysOf(t));
 }
 
 // a HUGEINT / UHUGEINT value as its 16-byte order key (cubit_key128), in a string for the
@@ -289,55 +301,33 @@ static string Key128(const Value &v) {
     return Key128(PhysicalType::UINT128, u.lower, u.upper);
 }
 
-// uploaded from 8-byte values (INT64, UINT32 widened, DOUBLE patterns; else from 4-byte ones)
-static bool WidePhysical(PhysicalType t) {
-    return t == PhysicalType::INT64 || t == PhysicalType::UINT32 || t == PhysicalType::UINT64 ||
-           t == PhysicalType::DOUBLE;
-}
+// ------------------------------------------------------------------ filters
 
-// the CUBIT_TYPE_* a column is registered as
-static int UploadType(PhysicalType t) {
-    switch (t) {
-    case PhysicalType::FLOAT:
-        return CUBIT_TYPE_FLOAT;
-    case PhysicalType::DOUBLE:
-        return CUBIT_TYPE_DOUBLE;
-    case PhysicalType::UINT64:
-        return CUBIT_TYPE_UINT64;
+// the CUBIT_CMP_* of a comparison a ConstantFilter may carry; -1 for any other expression type
+static int CmpOf(ExpressionType e) {
+    switch (e) {
+    case ExpressionType::COMPARE_EQUAL:
+        return CUBIT_CMP_EQ;
+    case ExpressionType::COMPARE_NOTEQUAL:
+        return CUBIT_CMP_NE;
+    case ExpressionType::COMPARE_LESSTHAN:
+        return CUBIT_CMP_LT;
+    case ExpressionType::COMPARE_LESSTHANOREQUALTO:
+        return CUBIT_CMP_LE;
+    case ExpressionType::COMPARE_GREATERTHAN:
+        return CUBIT_CMP_GT;
+    case ExpressionType::COMPARE_GREATERTHANOREQUALTO:
+        return CUBIT_CMP_GE;
     default:
-        return WidePhysical(t) ? CUBIT_TYPE_INT64 : CUBIT_TYPE_INT32;
+        return -1;
     }
-}
-
-static uint32_t FloatBits(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return u;
-}
-static int64_t DoubleBits(double d) {
-    int64_t b;
-    memcpy(&b, &d, 8);
-    return b;
 }
 
 static bool Supported(const TableFilter &f) {
     switch (f.filter_type) {
     case TableFilterType::CONSTANT_COMPARISON: {
         auto &c = f.Cast<ConstantFilter>();
-        if (!GpuPhysical(c.constant.type().InternalType())) {
-            return false;
-        }
-        switch (c.comparison_type) {
-        case ExpressionType::COMPARE_EQUAL:
-        case ExpressionType::COMPARE_NOTEQUAL:
-        case ExpressionType::COMPARE_LESSTHAN:
-        case ExpressionType::COMPARE_LESSTHANOREQUALTO:
-        case ExpressionType::COMPARE_GREATERTHAN:
-        case ExpressionType::COMPARE_GREATERTHANOREQUALTO:
-            return true;
-        default:
-            return false;
-        }
+        return Traits(c.constant.type().InternalType()).gpu && CmpOf(c.comparison_type) >= 0;
     }
     case TableFilterType::IS_NULL:
     case TableFilterType::IS_NOT_NULL:
@@ -361,32 +351,6 @@ static bool Supported(const TableFilter &f) {
     }
 }
 
-// one value of a flat vector of an integer-backed physical type, as int64
-static int64_t PhysicalAsInt64(Vector &v, idx_t i) {
-    switch (v.GetType().InternalType()) {
-    case PhysicalType::BOOL:
-        return FlatVector::GetData<bool>(v)[i] ? 1 : 0;
-    case PhysicalType::UINT8:
-        return FlatVector::GetData<uint8_t>(v)[i];
-    case PhysicalType::UINT16:
-        return FlatVector::GetData<uint16_t>(v)[i];
-    case PhysicalType::UINT32:
-        return FlatVector::GetData<uint32_t>(v)[i];
-    case PhysicalType::INT8:
-        return FlatVector::GetData<int8_t>(v)[i];
-    case PhysicalType::INT16:
-        return FlatVector::GetData<int16_t>(v)[i];
-    case PhysicalType::INT32:
-        return FlatVector::GetData<int32_t>(v)[i];
-    case PhysicalType::FLOAT:
-        return FloatBits(FlatVector::GetData<float>(v)[i]);  // the pattern, zero-extended
-    case PhysicalType::DOUBLE:
-        return DoubleBits(FlatVector::GetData<double>(v)[i]);
-    default:
-        return FlatVector::GetData<int64_t>(v)[i];
-    }
-}
-
 static int64_t ConstantAsInt64(const Value &v) {
     switch (v.type().InternalType()) {
     case PhysicalType::BOOL:
@@ -404,9 +368,9 @@ static int64_t ConstantAsInt64(const Value &v) {
     case PhysicalType::INT32:
         return v.GetValueUnsafe<int32_t>();  // DATE days, INTEGER, DECIMAL(≤9)
     case PhysicalType::FLOAT:
-        return FloatBits(v.GetValueUnsafe<float>());
+        return core::FloatBits(v.GetValueUnsafe<float>());
     case PhysicalType::DOUBLE:
-        return DoubleBits(v.GetValueUnsafe<double>());
+        return core::DoubleBits(v.GetValueUnsafe<double>());
     case PhysicalType::UINT64:
         return (int64_t)v.GetValueUnsafe<uint64_t>();  // the bits
     default:
@@ -430,26 +394,7 @@ static void Emit(const TableFilter &f, int32_t column, vector<cubit_filter_node>
     case TableFilterType::CONSTANT_COMPARISON: {
         auto &c = f.Cast<ConstantFilter>();
         n.kind = CUBIT_FILTER_CONSTANT;
-        switch (c.comparison_type) {
-        case ExpressionType::COMPARE_EQUAL:
-            n.cmp = CUBIT_CMP_EQ;
-            break;
-        case ExpressionType::COMPARE_NOTEQUAL:
-            n.cmp = CUBIT_CMP_NE;
-            break;
-        case ExpressionType::COMPARE_LESSTHAN:
-            n.cmp = CUBIT_CMP_LT;
-            break;
-        case ExpressionType::COMPARE_LESSTHANOREQUALTO:
-            n.cmp = CUBIT_CMP_LE;
-            break;
-        case ExpressionType::COMPARE_GREATERTHAN:
-            n.cmp = CUBIT_CMP_GT;
-            break;
-        default:
-            n.cmp = CUBIT_CMP_GE;
-            break;
-        }
+        n.cmp = CmpOf(c.comparison_type);  // one of the six: Supported admitted the filter
         const auto phys = c.constant.type().InternalType();
         if (phys == PhysicalType::VARCHAR) {
             const string &str = StringValue::Get(c.constant);
@@ -639,14 +584,6 @@ static unique_ptr<LocalTableFunctionState> CubitInitLocal(ExecutionContext &cont
     return std::move(l);
 }
 
-template <class T>
-static void Narrow(const int64_t *src, Vector &dst, idx_t n) {
-    auto d = FlatVector::GetData<T>(dst);
-    for (idx_t i = 0; i < n; i++) {
-        d[i] = (T)src[i];
-    }
-}
-
 // int64 staging → the column's physical type (DATE/INTEGER narrow, BIGINT/DECIMAL copy; VARCHAR
 // codes → the dictionary's strings, copied into the vector's string heap; a NULL row's code is 0
 // and its slot is left as the validity mask says)
@@ -657,7 +594,7 @@ static void CopyOut(const int64_t *src, Vector &dst, idx_t n, const uint64_t *va
         for (idx_t i = 0; i < n; i++) {
             const char *p = nullptr;
             uint64_t len = 0;
-            if (!((valid[i >> 6] >> (i & 63)) & 1) || !dict || cubit_dict_entry(dict, (uint64_t)src[i], &p, &len) != CUBIT_OK) {
+            if (!RowValid(valid, i) || !dict || cubit_dict_entry(dict, (uint64_t)src[i], &p, &len) != CUBIT_OK) {
                 d[i] = string_t();
                 continue;
             }
@@ -671,8 +608,7 @@ static void CopyOut(const int64_t *src, Vector &dst, idx_t n, const uint64_t *va
         for (idx_t i = 0; i < n; i++) {
             const char *p = nullptr;
             uint64_t len = 0, lower = 0, upper = 0;
-            if (((valid[i >> 6] >> (i & 63)) & 1) && dict && cubit_dict_entry(dict, (uint64_t)src[i], &p, &len) == CUBIT_OK &&
-                len == 16) {
+            if (RowValid(valid, i) && dict && cubit_dict_entry(dict, (uint64_t)src[i], &p, &len) == CUBIT_OK && len == 16) {
                 cubit_value128(is_signed ? CUBIT_TYPE_INT128 : CUBIT_TYPE_UINT128, (const unsigned char *)p, &lower,
                                &upper);
             }
@@ -684,49 +620,8 @@ static void CopyOut(const int64_t *src, Vector &dst, idx_t n, const uint64_t *va
         }
         break;
     }
-    case PhysicalType::BOOL:
-        Narrow<bool>(src, dst, n);
-        break;
-    case PhysicalType::UINT8:
-        Narrow<uint8_t>(src, dst, n);
-        break;
-    case PhysicalType::UINT16:
-        Narrow<uint16_t>(src, dst, n);
-        break;
-    case PhysicalType::UINT32:
-        Narrow<uint32_t>(src, dst, n);
-        break;
-    case PhysicalType::INT8: {
-        auto d = FlatVector::GetData<int8_t>(dst);
-        for (idx_t i = 0; i < n; i++) {
-            d[i] = (int8_t)src[i];
-        }
-        break;
-    }
-    case PhysicalType::INT16: {
-        auto d = FlatVector::GetData<int16_t>(dst);
-        for (idx_t i = 0; i < n; i++) {
-            d[i] = (int16_t)src[i];
-        }
-        break;
-    }
-    case PhysicalType::INT32: {
-        auto d = FlatVector::GetData<int32_t>(dst);
-        for (idx_t i = 0; i < n; i++) {
-            d[i] = (int32_t)src[i];
-        }
-        break;
-    }
-    case PhysicalType::FLOAT: {  // the 32-bit patterns back into the floats (DOUBLE: the 8-byte copy below)
-        auto d = FlatVector::GetData<float>(dst);
-        for (idx_t i = 0; i < n; i++) {
-            const uint32_t u = (uint32_t)src[i];
-            memcpy(d + i, &u, 4);
-        }
-        break;
-    }
-    default:
-        memcpy(FlatVector::GetData<int64_t>(dst), src, n * sizeof(int64_t));
+    default:  // the numeric types: narrowed, FLOAT from its patterns, 8-byte values copied
+        core::StoreFromInt64(PhysOf(dst.GetType().InternalType()), FlatVector::GetData(dst), src, n);
         break;
     }
 }
@@ -1161,7 +1056,7 @@ static void ReadRows(Connection &con, const string &table_name, DuckTableEntry &
     snap.present.clear();
     vector<bool> is_str(cols.size());
     for (idx_t c = 0; c < cols.size(); c++) {
-        is_str[c] = DictPhysical(entry.GetColumn(LogicalIndex(cols[c])).GetType().InternalType());
+        is_str[c] = Traits(entry.GetColumn(LogicalIndex(cols[c])).GetType().InternalType()).dict;
     }
     while (auto chunk = res->Fetch()) {
         chunk->Flatten();
@@ -1196,7 +1091,7 @@ static void ReadRows(Connection &con, const string &table_name, DuckTableEntry &
                 } else if (is_str[c]) {
                     snap.strings[c][r] = FlatVector::GetData<string_t>(vec)[i].GetString();
                 } else {
-                    snap.values[c][r] = PhysicalAsInt64(vec, i);
+                    snap.values[c][r] = core::LoadInt64(PhysOf(phys), FlatVector::GetData(vec), i);
                 }
             }
         }
@@ -1214,16 +1109,7 @@ static void ReadRows(Connection &con, const string &table_name, DuckTableEntry &
     }
 }
 
-// Strings as the bytes + offsets layout cubit_dict_create / cubit_dict_encode read (string i =
-// bytes[offsets[i], offsets[i+1]); an invalid row contributes an empty slot)
-static void PackStrings(const vector<string> &strs, vector<char> &bytes, vector<uint64_t> &offsets) {
-    bytes.clear();
-    offsets.assign(1, 0);
-    for (auto &x : strs) {
-        bytes.insert(bytes.end(), x.begin(), x.end());
-        offsets.push_back(bytes.size());
-    }
-}
+using core::PackStrings;
 
 // A VARCHAR column of a snapshot as its table-wide dictionary (its valid strings) and every row's
 // code (NULL rows: 0); the caller owns the dictionary.
@@ -1260,7 +1146,7 @@ static cubit_dict *EncodeStrings(const vector<string> &strs, const vector<uint64
                                  cubit_ctx *ctx = nullptr) {
     vector<string> valid_strs;
     for (idx_t r = 0; r < strs.size(); r++) {
-        if ((validity[r >> 6] >> (r & 63)) & 1) {
+        if (RowValid(validity.data(), r)) {
             valid_strs.push_back(strs[r]);
         }
     }
@@ -1286,7 +1172,7 @@ static cubit_dict *EncodeStrings(const vector<string> &strs, const vector<uint64
 // dictionary; a new string makes the sync rebuild with a new one)
 static bool StringsInDict(cubit_dict *d, const vector<string> &strs, const vector<uint64_t> &validity) {
     for (idx_t r = 0; r < strs.size(); r++) {
-        if (!((validity[r >> 6] >> (r & 63)) & 1)) {
+        if (!RowValid(validity.data(), r)) {
             continue;
         }
         uint64_t lb = 0;
@@ -1298,50 +1184,8 @@ static bool StringsInDict(cubit_dict *d, const vector<string> &strs, const vecto
     return true;
 }
 
-// Every distinct value when the column has at most this many (l_discount 11, l_quantity 50);
-// a column with more gets no index unless the attach names one (l_shipdate's 2,526 distinct
-// dates would take 2,526 bitvectors, 190 GB at SF100): its comparisons are built from the raw
-// column at scan time (K0).
-static constexpr idx_t kDefaultDistinctIndexMax = 256;
-
-static bool FewDistinct(const vector<int64_t> &v, const vector<uint64_t> &valid) {
-    unordered_set<int64_t> seen;
-    for (idx_t r = 0; r < v.size(); r++) {
-        if ((valid[r >> 6] >> (r & 63)) & 1) {
-            seen.insert(v[r]);
-            if (seen.size() > kDefaultDistinctIndexMax) {
-                return false;
-            }
-        }
-    }
-    return true;
-}
-
-// The CUBIT_TYPE_* of a column's BITPACKING segments: the T DuckDB packs its physical type
-// with (bitpacking.cpp:953-977, BOOL as int8_t); -1 for a type the partition does not hold.
-static int SegmentType(PhysicalType t) {
-    switch (t) {
-    case PhysicalType::BOOL:
-    case PhysicalType::INT8:
-        return CUBIT_TYPE_INT8;
-    case PhysicalType::INT16:
-        return CUBIT_TYPE_INT16;
-    case PhysicalType::INT32:
-        return CUBIT_TYPE_INT32;
-    case PhysicalType::INT64:
-        return CUBIT_TYPE_INT64;
-    case PhysicalType::UINT8:
-        return CUBIT_TYPE_UINT8;
-    case PhysicalType::UINT16:
-        return CUBIT_TYPE_UINT16;
-    case PhysicalType::UINT32:
-        return CUBIT_TYPE_UINT32;
-    case PhysicalType::UINT64:
-        return CUBIT_TYPE_UINT64;
-    default:
-        return -1;
-    }
-}
+using core::FewDistinct;
+using core::kDefaultDistinctIndexMax;
 
 // K5 from the database file: when every segment of column `col` is a persistent BITPACKING
 // segment without in-memory updates and together they hold rows [0, n_rows) in order, the
@@ -1363,14 +1207,12 @@ static int SegmentType(PhysicalType t) {
 // list); updates make has_updates true and keep this path off.
 static bool AttachSegmentColumn(DuckTableEntry &entry, column_t col, PhysicalType ptype, uint64_t n_rows,
                                 cubit_table *t, const uint64_t *validity) {
-    const int seg_type = SegmentType(ptype);
-    if (seg_type < 0 || n_rows == 0) {
+    const auto traits = Traits(ptype);
+    if (traits.segment_type < 0 || n_rows == 0) {
         return false;
     }
     auto &storage = entry.GetStorage();
     const string path = "[" + to_string(col) + "]";
-    const string bitpacking = CompressionTypeToString(CompressionType::COMPRESSION_BITPACKING);
-    const string rle = CompressionTypeToString(CompressionType::COMPRESSION_RLE);
     vector<ColumnSegmentInfo> segs;
     for (auto &info : storage.GetColumnSegmentInfo()) {
         if (info.column_id == col && info.column_path == path) {
@@ -1380,112 +1222,62 @@ static bool AttachSegmentColumn(DuckTableEntry &entry, column_t col, PhysicalTyp
     std::sort(segs.begin(), segs.end(), [](const ColumnSegmentInfo &a, const ColumnSegmentInfo &b) {
         return a.segment_start < b.segment_start;
     });
-    // the codecs the GPU reads: BITPACKING (unpacked), RLE (runs expanded), CONSTANT (one value,
-    // from the segment's statistics), UNCOMPRESSED (the values); one codec for every segment keeps
-    // its own entry point (a BITPACKING column keeps its segments for the packed filter)
-    const string constant = CompressionTypeToString(CompressionType::COMPRESSION_CONSTANT);
-    const string uncompressed = CompressionTypeToString(CompressionType::COMPRESSION_UNCOMPRESSED);
-    const auto &ltype = entry.GetColumn(LogicalIndex(col)).GetType();
-    vector<int32_t> codecs;
-    vector<int64_t> constants;
-    uint64_t next = 0;
+    std::vector<core::SegmentDesc> descs;
     for (auto &sg : segs) {
-        if (sg.has_updates || sg.segment_start != next) {
-            return false;
-        }
-        const string &c = sg.compression_type;
-        int32_t codec = -1;
-        int64_t value = 0;
-        if (c == bitpacking) {
-            codec = CUBIT_CODEC_BITPACKING;
-        } else if (c == rle) {
-            codec = CUBIT_CODEC_RLE;
-        } else if (c == uncompressed) {
-            codec = CUBIT_CODEC_UNCOMPRESSED;
-        } else if (c == constant) {
-            // ConstantScanFunction reads NumericStats::Min (compression/numeric_constant.cpp); the
-            // public ColumnSegmentInfo carries it as text ("[Min: v, Max: v][Has Null: …]"),
-            // parsed back through the column's type (DATE, DECIMAL and BOOL print as literals)
-            const string &st = sg.segment_stats;
-            const auto a = st.find("[Min: "), b = st.find(", Max: ");
-            if (a != 0 || b == string::npos) {
+        descs.push_back({sg.segment_start, sg.segment_count, sg.compression_type, sg.has_updates, sg.persistent,
+                         sg.segment_stats});
+    }
+    const core::CodecNames names {CompressionTypeToString(CompressionType::COMPRESSION_BITPACKING),
+                                  CompressionTypeToString(CompressionType::COMPRESSION_RLE),
+                                  CompressionTypeToString(CompressionType::COMPRESSION_CONSTANT),
+                                  CompressionTypeToString(CompressionType::COMPRESSION_UNCOMPRESSED)};
+    std::vector<int32_t> codecs;
+    if (!core::PlanSegments(descs, n_rows, names, codecs)) {
+        return false;
+    }
+    const auto &ltype = entry.GetColumn(LogicalIndex(col)).GetType();
+    auto &block_manager = TableIOManager::Get(storage).GetBlockManagerForRowData();
+    core::SegmentImages im;
+    vector<int64_t> constants(segs.size(), 0);
+    for (size_t i = 0; i < segs.size(); i++) {
+        auto &sg = segs[i];
+        if (codecs[i] == CUBIT_CODEC_CONSTANT) {
+            // the statistics' minimum, parsed back through the column's type (core::ConstantMinLiteral)
+            string lit;
+            bool is_null = false;
+            if (!core::ConstantMinLiteral(descs[i].stats, lit, is_null)) {
                 return false;
             }
-            const string lit = st.substr(6, b - 6);
-            if (lit != "NULL") {  // an all-NULL segment: any value
+            if (!is_null) {  // an all-NULL segment: any value
                 try {
-                    value = ConstantAsInt64(Value(lit).DefaultCastAs(ltype));
+                    constants[i] = ConstantAsInt64(Value(lit).DefaultCastAs(ltype));
                 } catch (std::exception &) {
                     return false;
                 }
             }
-            codec = CUBIT_CODEC_CONSTANT;
-        }
-        if (codec < 0 || (codec != CUBIT_CODEC_CONSTANT && !sg.persistent)) {
-            return false;
-        }
-        codecs.push_back(codec);
-        constants.push_back(value);
-        next += sg.segment_count;
-    }
-    if (next != n_rows || segs.empty()) {
-        return false;
-    }
-    const int tsz = ptype == PhysicalType::BOOL || ptype == PhysicalType::INT8 || ptype == PhysicalType::UINT8 ? 1
-                    : ptype == PhysicalType::INT16 || ptype == PhysicalType::UINT16                        ? 2
-                    : ptype == PhysicalType::INT32 || ptype == PhysicalType::UINT32                        ? 4
-                                                                                                           : 8;
-    auto &block_manager = TableIOManager::Get(storage).GetBlockManagerForRowData();
-    vector<uint8_t> bytes;
-    vector<uint64_t> offsets, rows;
-    for (size_t i = 0; i < segs.size(); i++) {
-        auto &sg = segs[i];
-        const uint64_t at = (bytes.size() + 15) / 16 * 16;
-        offsets.push_back(at);
-        rows.push_back(sg.segment_count);
-        if (codecs[i] == CUBIT_CODEC_CONSTANT) {
-            continue;  // no bytes
+            core::AppendSegment(im, codecs[i], nullptr, 0, sg.segment_count, traits.width);  // no bytes
+            continue;
         }
         auto handle = block_manager.RegisterBlock(sg.block_id);
         auto pin = block_manager.buffer_manager.Pin(handle);
-        const_data_ptr_t p = pin.Ptr() + sg.block_offset;
-        const uint64_t room = block_manager.GetBlockSize() - sg.block_offset;
-        uint64_t size = 0;
-        if (codecs[i] == CUBIT_CODEC_UNCOMPRESSED) {
-            size = sg.segment_count * tsz;  // the values from the segment's start (FixedSizeScan)
-            if (size > room) {
-                return false;
-            }
-        } else {
-            memcpy(&size, p, sizeof(size));  // BITPACKING: the segment's size; RLE: where its run lengths start
-            if (size < 8 || size > room) {
-                return false;  // not a segment header
-            }
+        if (!core::AppendSegment(im, codecs[i], pin.Ptr() + sg.block_offset,
+                                 block_manager.GetBlockSize() - sg.block_offset, sg.segment_count, traits.width)) {
+            return false;  // not a segment image that fits its block
         }
-        if (codecs[i] == CUBIT_CODEC_RLE) {  // the run lengths end the segment: read them until they cover its rows
-            uint64_t covered = 0, k = 0;
-            while (covered < sg.segment_count) {
-                if (size + 2 * (k + 1) > room) {
-                    return false;
-                }
-                uint16_t len;
-                memcpy(&len, p + size + 2 * k++, 2);
-                covered += len;
-            }
-            size += 2 * k;
-        }
-        bytes.resize(at + size, 0);
-        memcpy(bytes.data() + at, p, size);
     }
-    const bool all_bp = std::all_of(codecs.begin(), codecs.end(), [](int32_t c) { return c == CUBIT_CODEC_BITPACKING; });
-    const bool all_rle = std::all_of(codecs.begin(), codecs.end(), [](int32_t c) { return c == CUBIT_CODEC_RLE; });
-    if (all_bp || all_rle) {
-        auto add = all_rle ? cubit_table_add_rle_column : cubit_table_add_bitpacked_column;
-        return add(t, (int)col, seg_type, bytes.data(), bytes.size(), offsets.data(), rows.data(), (uint32_t)segs.size(),
-                   validity) == CUBIT_OK;
+    const auto n_segs = (uint32_t)segs.size();
+    switch (core::ChooseEntry(codecs)) {
+    case core::SegmentEntry::Bitpacked:
+        return cubit_table_add_bitpacked_column(t, (int)col, traits.segment_type, im.bytes.data(), im.bytes.size(),
+                                                im.offsets.data(), im.rows.data(), n_segs, validity) == CUBIT_OK;
+    case core::SegmentEntry::Rle:
+        return cubit_table_add_rle_column(t, (int)col, traits.segment_type, im.bytes.data(), im.bytes.size(),
+                                          im.offsets.data(), im.rows.data(), n_segs, validity) == CUBIT_OK;
+    default:
+        return cubit_table_add_segment_column(t, (int)col, traits.segment_type, im.bytes.data(), im.bytes.size(),
+                                              im.offsets.data(), im.rows.data(), codecs.data(), constants.data(), n_segs,
+                                              validity) == CUBIT_OK;
     }
-    return cubit_table_add_segment_column(t, (int)col, seg_type, bytes.data(), bytes.size(), offsets.data(), rows.data(),
-                                          codecs.data(), constants.data(), (uint32_t)segs.size(), validity) == CUBIT_OK;
 }
 
 // The column as registered against the snapshot's values on a sample (the valid rows of a
@@ -1494,13 +1286,7 @@ static bool AttachSegmentColumn(DuckTableEntry &entry, column_t col, PhysicalTyp
 // snapshot (the file moved on under it) falls back to the decoded values.
 static bool SampleMatches(cubit_ctx *ctx, cubit_table *t, column_t col, const vector<int64_t> &values,
                           const vector<uint64_t> &validity, uint64_t n) {
-    vector<int64_t> ids;
-    const uint64_t stride = std::max<uint64_t>(1, n / 4096);
-    for (uint64_t r = 0; r < n && ids.size() < 4096; r += stride) {
-        if ((validity[r >> 6] >> (r & 63)) & 1) {
-            ids.push_back((int64_t)r);
-        }
-    }
+    const std::vector<int64_t> ids = core::SampleRows(validity.data(), n);
     if (ids.empty()) {
         return true;
     }
@@ -1542,13 +1328,12 @@ static std::shared_ptr<CubitPartitionSet> BuildPartition(CubitAttached &attached
     auto set = std::make_shared<CubitPartitionSet>();
     set->contexts = attached.contexts;
     const auto &ctxs = set->contexts->ctxs;
-    const uint64_t rg = 122880, units = (snap.rows + rg - 1) / rg;
-    const uint64_t n_parts = std::max<uint64_t>(1, std::min<uint64_t>(ctxs.size(), units));
+    const core::PartitionSplit split(snap.rows, ctxs.size());
     vector<bool> few(attached.column_order.size());
     vector<vector<int32_t>> codes(attached.column_order.size());  // dictionary columns: every row's code
     for (idx_t c = 0; c < attached.column_order.size(); c++) {
         const column_t col = attached.column_order[c];
-        if (DictPhysical(attached.columns[col])) {
+        if (Traits(attached.columns[col]).dict) {
             cubit_dict *d = EncodeStrings(snap.strings[c], snap.validity[c], codes[c], ctxs[0]);
             set->dicts[col] = d;  // the set owns it from here (its destructor frees it)
             uint64_t size = 0;
@@ -1558,9 +1343,8 @@ static std::shared_ptr<CubitPartitionSet> BuildPartition(CubitAttached &attached
             few[c] = FewDistinct(snap.values[c], snap.validity[c]);
         }
     }
-    for (uint64_t p = 0; p < n_parts; p++) {
-        const uint64_t b = std::min(snap.rows, units * p / n_parts * rg);
-        const uint64_t e = std::min(snap.rows, units * (p + 1) / n_parts * rg);
+    for (uint64_t p = 0; p < split.n_parts; p++) {
+        const uint64_t b = split.Begin(p), e = split.End(p);
         cubit_table *t = nullptr;
         Check(cubit_table_create(ctxs[p], e - b, (int64_t)b, &t));
         set->parts.push_back(t);
@@ -1568,21 +1352,22 @@ static std::shared_ptr<CubitPartitionSet> BuildPartition(CubitAttached &attached
         for (idx_t c = 0; c < attached.column_order.size(); c++) {
             const column_t col = attached.column_order[c];
             const uint64_t *valid = snap.validity[c].data() + b / 64;
-            if (DictPhysical(attached.columns[col])) {
+            const auto traits = Traits(attached.columns[col]);
+            if (traits.dict) {
                 Check(cubit_table_add_dict_column(t, (int)col, set->dicts[col], codes[c].data() + b, valid, 0));
             }
             const bool from_segments =
-                !DictPhysical(attached.columns[col]) && entry && n_parts == 1 &&
+                !traits.dict && entry && split.n_parts == 1 &&
                 AttachSegmentColumn(*entry, col, attached.columns[col], snap.rows, t, valid) &&
                 SampleMatches(ctxs[p], t, col, snap.values[c], snap.validity[c], snap.rows);
-            if (!from_segments && !DictPhysical(attached.columns[col])) {
+            if (!from_segments && !traits.dict) {
                 // (re-)registering replaces a column taken from segments
-                const bool wide = WidePhysical(attached.columns[col]);
+                const bool wide = traits.wide;
                 vector<int32_t> narrow;
                 if (!wide) {
                     narrow.assign(snap.values[c].begin() + b, snap.values[c].begin() + e);
                 }
-                Check(cubit_table_add_column(t, (int)col, UploadType(attached.columns[col]),
+                Check(cubit_table_add_column(t, (int)col, traits.upload_type,
                                              wide ? (const void *)(snap.values[c].data() + b) : (const void *)narrow.data(),
                                              valid, 0));
             }
@@ -1612,23 +1397,10 @@ static std::shared_ptr<CubitPartitionSet> BuildPartition(CubitAttached &attached
 // The committed deletes (row ids the snapshot lacks, visible to every snapshot the swap admits:
 // start_time >= the sync's) as each partition's delete list of local rows.
 static void SetDeletes(CubitPartitionSet &set, const vector<bool> &present, uint64_t rows) {
-    vector<int64_t> gone;
-    for (uint64_t r = 0; r < rows; r++) {
-        if (r >= present.size() || !present[r]) {
-            gone.push_back((int64_t)r);
-        }
-    }
+    const auto local = core::LocalDeletes(present, rows, set.part_base);
     for (size_t p = 0; p < set.parts.size(); p++) {
-        const int64_t b = (int64_t)set.part_base[p];
-        const int64_t e = p + 1 < set.parts.size() ? (int64_t)set.part_base[p + 1] : (int64_t)rows;
-        vector<int64_t> local;
-        for (auto r : gone) {
-            if (r >= b && r < e) {
-                local.push_back(r - b);
-            }
-        }
-        vector<uint64_t> ids(local.size(), 0);
-        Check(cubit_table_set_deletes(set.parts[p], local.data(), ids.data(), local.size()));
+        vector<uint64_t> ids(local[p].size(), 0);
+        Check(cubit_table_set_deletes(set.parts[p], local[p].data(), ids.data(), local[p].size()));
     }
 }
 
@@ -1741,7 +1513,7 @@ static void SyncPartition(ClientContext &context, DuckTableEntry &entry, CubitAt
         for (idx_t c = 0; c < attached.column_order.size(); c++) {
             const column_t col = attached.column_order[c];
             cols.push_back((int)col);
-            if (DictPhysical(attached.columns[col])) {  // codes in the kept dictionary
+            if (Traits(attached.columns[col]).dict) {  // codes in the kept dictionary
                 vector<char> bytes;
                 vector<uint64_t> offsets;
                 PackStrings(snap.strings[c], bytes, offsets);
@@ -1749,7 +1521,7 @@ static void SyncPartition(ClientContext &context, DuckTableEntry &entry, CubitAt
                 Check(cubit_dict_encode(cur->dicts.at(col), bytes.data(), offsets.data(), snap.rows,
                                         snap.validity[c].data(), narrow.back().data()));
                 data.push_back(narrow.back().data());
-            } else if (WidePhysical(attached.columns[col])) {
+            } else if (Traits(attached.columns[col]).wide) {
                 data.push_back(snap.values[c].data());
             } else {
                 narrow.emplace_back(snap.values[c].begin(), snap.values[c].end());
@@ -1782,66 +1554,43 @@ static void CubitSync(ClientContext &context, const FunctionParameters &paramete
     SyncPartition(context, entry.Cast<DuckTableEntry>(), *attached, table_name, false);
 }
 
-// Index specification of cubit_attach's third argument: `column=encoding[:v1,v2,…]` items
-// separated by ';' — encoding range | equality | bins, values as SQL literals of the column's
-// type (dates, decimals), e.g.
-//   'l_shipdate=range:1994-01-01,1995-01-01;l_shipdate=bins:1992-01-01,1993-01-01,…;l_discount=range'
+// Index specification of cubit_attach's third argument (core::SplitIndexSpec splits the text):
+// the columns resolved against the table, the literals cast to each column's type, the keys
+// sorted. The items before a malformed one are resolved first, so errors come in item order.
 static vector<CubitIndexSpec> ParseIndexSpec(DuckTableEntry &entry, const string &spec) {
+    std::vector<core::IndexItem> items;
+    string bad;
+    const auto status = core::SplitIndexSpec(spec, items, bad);
     vector<CubitIndexSpec> out;
-    for (auto item : StringUtil::Split(spec, ';')) {
-        StringUtil::Trim(item);
-        if (item.empty()) {
-            continue;
-        }
-        const auto eq = item.find('=');
-        if (eq == string::npos) {
-            throw InvalidInputException("cubit_attach: index item '%s' is not column=encoding[:values]", item);
-        }
-        auto name = item.substr(0, eq);
-        auto rest = item.substr(eq + 1);
-        StringUtil::Trim(name);
-        const auto colon = rest.find(':');
-        auto enc = StringUtil::Lower(rest.substr(0, colon));
-        StringUtil::Trim(enc);
-        const auto &def = entry.GetColumn(name);
+    for (auto &item : items) {
+        const auto &def = entry.GetColumn(item.name);
         CubitIndexSpec ix;
         ix.column = def.StorageOid();
-        if (enc == "range") {
-            ix.encoding = CUBIT_INDEX_RANGE;
-        } else if (enc == "equality") {
-            ix.encoding = CUBIT_INDEX_EQUALITY;
-        } else if (enc == "bins") {
-            ix.encoding = CUBIT_INDEX_BINS;
-        } else {
-            throw InvalidInputException("cubit_attach: unknown index encoding '%s'", enc);
-        }
+        ix.encoding = item.encoding;
         const auto phys = def.GetType().InternalType();
-        if (colon != string::npos && DictPhysical(phys)) {
-            for (auto lit : StringUtil::Split(rest.substr(colon + 1), ',')) {
-                StringUtil::Trim(lit);
-                // byte order = DuckDB's string order (string_type.hpp:176-206); HUGEINT / UHUGEINT
-                // literals as their order keys (byte order = the values' order)
+        if (Traits(phys).dict) {
+            for (auto &lit : item.literals) {
+                // HUGEINT / UHUGEINT literals as their order keys
                 ix.str_keys.push_back(phys == PhysicalType::VARCHAR ? lit
                                                                     : Key128(Value(lit).DefaultCastAs(def.GetType())));
             }
-            std::sort(ix.str_keys.begin(), ix.str_keys.end());
-            ix.str_keys.erase(std::unique(ix.str_keys.begin(), ix.str_keys.end()), ix.str_keys.end());
-        } else if (colon != string::npos) {
-            for (auto lit : StringUtil::Split(rest.substr(colon + 1), ',')) {
-                StringUtil::Trim(lit);
+            core::SortKeys(ix.str_keys);
+        } else {
+            for (auto &lit : item.literals) {
                 ix.keys.push_back(ConstantAsInt64(Value(lit).DefaultCastAs(def.GetType())));
             }
-            // ascending in the column's order (FLOAT / DOUBLE patterns by their comparison keys)
-            const int type = UploadType(def.GetType().InternalType());
-            auto key = [type](int64_t v) { return cubit_fp_key(type, v); };
-            std::sort(ix.keys.begin(), ix.keys.end(), [&](int64_t a, int64_t b) { return key(a) < key(b); });
-            ix.keys.erase(std::unique(ix.keys.begin(), ix.keys.end(), [&](int64_t a, int64_t b) { return key(a) == key(b); }),
-                          ix.keys.end());
+            core::SortKeys(Traits(phys).upload_type, ix.keys);
         }
-        if (ix.encoding == CUBIT_INDEX_BINS && ix.keys.size() + ix.str_keys.size() < 2) {
-            throw InvalidInputException("cubit_attach: bins on %s need at least two edges", name);
+        if (!core::EnoughKeys(ix.encoding, ix.keys.size() + ix.str_keys.size())) {
+            throw InvalidInputException("cubit_attach: bins on %s need at least two edges", item.name);
         }
         out.push_back(std::move(ix));
+    }
+    if (status == core::SpecStatus::MissingEquals) {
+        throw InvalidInputException("cubit_attach: index item '%s' is not column=encoding[:values]", bad);
+    }
+    if (status == core::SpecStatus::UnknownEncoding) {
+        throw InvalidInputException("cubit_attach: unknown index encoding '%s'", bad);
     }
     return out;
 }
@@ -1883,7 +1632,7 @@ static void CubitAttachImpl(ClientContext &context, const string &table_name, co
             StringUtil::Trim(name);
             const auto &def = duck.GetColumn(name);
             const auto phys = def.GetType().InternalType();
-            if (!GpuPhysical(phys)) {
+            if (!Traits(phys).gpu) {
                 throw InvalidInputException("cubit_attach: column %s is not integer-, FLOAT- or DOUBLE-backed", name);
             }
             attached.columns[def.StorageOid()] = phys;
