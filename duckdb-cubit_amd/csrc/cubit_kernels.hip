@@ -1518,7 +1518,7 @@ __global__ __launch_bounds__(512, 4) void eval_sum_product(EvalArgs a, SumArgs s
         const uint64_t r = (uint64_t)(row - a.row_base);
         if (s.a_valid && !((s.a_valid[r >> 6] >> (r & 63)) & 1ull)) return;
         int64_t bv = bval_decoded;
-        if (M == 0) {
+        if (M == 0 && s.b) {  // gathered b (b = nullptr with M = 0: the filter pins b to v0 alone)
             if (s.b_valid && !((s.b_valid[r >> 6] >> (r & 63)) & 1ull)) return;
             bv = s.b[r];
         }
@@ -1619,7 +1619,7 @@ __global__ __launch_bounds__(512, 4) void eval_sum_product(EvalArgs a, SumArgs s
                     const uint64_t rr = (uint64_t)(row0 - a.row_base) + (sr & ((1u << kMissShift) - 1));
                     // line-granular gathers, no reuse: nontemporal like the leaf loads
                     av[u] = ok[u] ? load_a(rr) : 0;
-                    bvv[u] = M > 0 ? (ok[u] ? decoded_b(sr >> kMissShift) : 0) : (ok[u] ? __builtin_nontemporal_load(s.b + rr) : 0);
+                    bvv[u] = M > 0 ? (ok[u] ? decoded_b(sr >> kMissShift) : 0) : (ok[u] ? (s.b ? __builtin_nontemporal_load(s.b + rr) : s.v0) : 0);
                     if (ok[u] && s.a_valid && !((s.a_valid[rr >> 6] >> (rr & 63)) & 1ull)) ok[u] = false;
                     if (M == 0 && ok[u] && s.b_valid && !((s.b_valid[rr >> 6] >> (rr & 63)) & 1ull)) ok[u] = false;
                 }

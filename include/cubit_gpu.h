@@ -622,7 +622,8 @@ int cubit_table_last_zones(cubit_table *t, uint32_t *evaluated, uint32_t *zones)
 #define CUBIT_SUM_PLAIN_A 8u
 int cubit_table_sum_product(cubit_table *t, const cubit_filter_node *nodes, uint32_t n_nodes, const cubit_txn *txn,
                             int col_a, int col_b, int64_t *d_out, uint64_t *d_count, uint32_t flags);
-/* How the last sum_product read b: number of values decoded from the index (0 = gathered). */
+/* How the last sum_product read b: number of values decoded from the index (0 = gathered;
+ * 1 = the filter pins b to one value, which is multiplied in as a constant: no leaf is read). */
 int cubit_table_last_sum_decode(cubit_table *t, uint32_t *n_values);
 /* Whether the last sum_product read a from its BITPACKING segments. */
 int cubit_table_last_sum_packed(cubit_table *t, int *packed);

@@ -217,11 +217,17 @@ static int can_store(const bp_writer *w, uint64_t data_bytes, uint64_t meta_byte
     return req_data + req_meta <= w->block_size - 8;
 }
 
-static void reserve(bp_writer *w, uint64_t data_bytes) {
-    if (!can_store(w, data_bytes, 4)) {
+/* Room for one group in the current segment, or in a fresh one; 0 (and failed = 2) when the group
+ * does not fit in an empty segment of block_size bytes: nothing may be written then */
+static int reserve(bp_writer *w, uint64_t data_bytes) {
+    if (can_store(w, data_bytes, 4)) return 1;
+    if (w->seg_rows) {
         seg_flush(w);
         seg_begin(w);
+        if (can_store(w, data_bytes, 4)) return 1;
     }
+    w->failed = 2;
+    return 0;
 }
 
 static void write_meta(bp_writer *w, int mode) {
@@ -270,7 +276,7 @@ static int st_flush(bp_state *s, bp_writer *w) {
     uint64_t *cb = s->buf + 1;
     if (s->idx == 0) return 1;
     if ((s->all_invalid || s->maximum == s->minimum) && (s->mode == BP_AUTO || s->mode == BP_CONSTANT)) {
-        reserve(w, ts);
+        if (!reserve(w, ts)) return 0;
         write_meta(w, BP_CONSTANT);
         put_t(w, s->maximum);
         w->seg_rows += s->idx;
@@ -302,7 +308,7 @@ static int st_flush(bp_state *s, bp_writer *w) {
     }
     if (s->can_delta) {
         if (s->max_delta == s->min_delta && s->mode != BP_FOR && s->mode != BP_DELTA_FOR) {
-            reserve(w, 2 * ts);
+            if (!reserve(w, 2 * ts)) return 0;
             write_meta(w, BP_CONSTANT_DELTA);
             put_t(w, cb[0]);
             put_t(w, s->max_delta);
@@ -315,7 +321,7 @@ static int st_flush(bp_state *s, bp_writer *w) {
             uint64_t u[BP_GROUP];
             for (uint64_t i = 0; i < s->idx; i++) u[i] = (s->delta[i] - s->min_delta) & t.mask;
             const uint64_t bp = (s->idx + BP_ALG - 1) / BP_ALG * BP_ALG * (uint64_t)dw / 8;
-            reserve(w, bp + 3 * ts);
+            if (!reserve(w, bp + 3 * ts)) return 0;
             write_meta(w, BP_DELTA_FOR);
             put_t(w, s->min_delta);
             put_t(w, (uint64_t)dw);
@@ -331,7 +337,7 @@ static int st_flush(bp_state *s, bp_writer *w) {
         uint64_t u[BP_GROUP];
         for (uint64_t i = 0; i < s->idx; i++) u[i] = (cb[i] - s->minimum) & t.mask;
         const uint64_t bp = (s->idx + BP_ALG - 1) / BP_ALG * BP_ALG * (uint64_t)fw / 8;
-        reserve(w, bp + 2 * ts);
+        if (!reserve(w, bp + 2 * ts)) return 0;
         write_meta(w, BP_FOR);
         put_t(w, s->minimum);
         put_t(w, (uint64_t)fw);
@@ -347,6 +353,7 @@ int oracle_bp_compress(const void *values, int ttype, const uint8_t *valid, uint
                        uint8_t *out, uint64_t out_cap, uint64_t *seg_off, uint64_t *seg_size, uint64_t *seg_count,
                        uint32_t max_segs, uint32_t *n_segs) {
     if (!bp_ttype_ok(ttype) || !values || !out || !n_segs) return -1;
+    if (block_size < 16) return -3; /* the segment header and one metadata entry */
     const bp_t t = bp_type(ttype);
     bp_writer w;
     memset(&w, 0, sizeof(w));
@@ -391,6 +398,7 @@ int oracle_bp_compress(const void *values, int ttype, const uint8_t *valid, uint
     if (ok) seg_flush(&w);
     free(w.blk);
     free(s);
+    if (w.failed == 2) return -3; /* a group larger than a segment of block_size bytes */
     if (!ok) return 1;    /* not bitpackable (the reference picks another compression) */
     if (w.failed) return -2;
     *n_segs = w.n_segs;

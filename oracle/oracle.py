@@ -421,6 +421,8 @@ def bp_compress(values: np.ndarray, valid: Optional[np.ndarray] = None, mode: st
                                   sc.ctypes.data, max_segs, C.byref(ns))
     if rc == 1:
         return None
+    if rc == -3:
+        raise ValueError(f"block_size {block_size} cannot hold one group of these values")
     assert rc == 0, rc
     k = ns.value
     used = int(so[k - 1] + ss[k - 1]) if k else 0

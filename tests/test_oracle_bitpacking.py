@@ -56,6 +56,26 @@ def test_round_trips_and_segments(mode):
     assert len(big.seg_off) > 1 and np.all(big.seg_size <= O.DUCKDB_BLOCK_SIZE)
 
 
+@pytest.mark.parametrize("mode", ["for", "delta_for", "auto"])
+def test_group_larger_than_the_block_is_an_error(mode):
+    """A 2,048-row group of 24-bit values packs to 6,144 bytes: a 4,096-byte block cannot hold it,
+    and the compressor says so instead of writing past its segment image. A block with just the
+    room for it (header 8 + FOR's minimum and width 16 + 6,144 + metadata 4, and the 8 bytes the
+    reference keeps free) still round-trips, one group per segment."""
+    rng = np.random.default_rng(24)
+    v = rng.integers(0, 2 ** 24, 5000).astype(np.int64)
+    v[0], v[1] = 0, 2 ** 24 - 1
+    for bs in (0, 8, 4096, 6144):
+        with pytest.raises(ValueError):
+            O.bp_compress(v, None, mode, block_size=bs)
+    c = O.bp_compress(v, None, mode, block_size=6184)
+    assert np.array_equal(O.bp_decode(c), v) and list(c.seg_count) == [2048, 2048, 904]
+    # the values before the oversized group do not leak out as a partial column either
+    w = np.concatenate([np.full(4096, 7, np.int64), v])
+    with pytest.raises(ValueError):
+        O.bp_compress(w, None, mode, block_size=4096)
+
+
 def test_nulls_and_all_null_groups():
     rng = np.random.default_rng(6)
     v = rng.integers(0, 500, 10_000).astype(np.int32)
