@@ -1581,6 +1581,12 @@ bool host_timing() {
     static const bool on = std::getenv("CUBIT_HOST_TIMING") != nullptr;
     return on;
 }
+// CUBIT_SYNC_TIMING: cubit_table_sync_column prints its phases (host time, the stream synchronised
+// at each boundary) on stderr (diagnostic; scripts/sync_timing.py)
+bool sync_timing() {
+    static const bool on = std::getenv("CUBIT_SYNC_TIMING") != nullptr;
+    return on;
+}
 uint64_t now_ns() {
     return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
                std::chrono::steady_clock::now().time_since_epoch())
@@ -2901,6 +2907,70 @@ extern "C" int cubit_table_append(cubit_table* t, uint64_t n_new, const int* col
     return CUBIT_OK;
 }
 
+namespace {
+
+// The second half of a merge, shared by cubit_table_merge_updates and cubit_table_sync_column:
+// the m records (device lists, rows ascending, one record per row; valid_p null = every record
+// carries its value, a NULL record holds value 0) written into the base values, the validity and
+// every index bitvector of the column (merge_words_kernel). `added` = the records' distinct valid
+// values as keys, ascending (the statistics and exact keys they add); any_null = some record is
+// NULL (the column then needs a validity bitvector).
+int apply_records(cubit_table* t, int col, Column& c, const int64_t* rows_p, const int64_t* vals_p,
+                  const uint8_t* valid_p, uint64_t m, const std::vector<int64_t>& added, bool any_null) {
+    hipStream_t s = t->ctx->stream;
+    HIP_CHECK(hipStreamSynchronize(s));
+    drop_zones(t);  // the merge rewrites index words in place
+    if (int rc = own_column(t, c, std::max<uint64_t>(t->n_rows, c.cap_rows))) return rc;
+    if (any_null)
+        if (int rc = ensure_validity(t, c)) return rc;
+    c.drop_packed();  // merged values are not in the segments
+    Index* ixs[2] = {t->idx.count(col) ? &t->idx[col] : nullptr, t->bins.count(col) ? &t->bins[col] : nullptr};
+    MergeIndex mi[2] = {};
+    DevBuf d_keys[2], d_bvs[2];
+    for (int x = 0; x < 2; ++x) {
+        Index* ix = ixs[x];
+        if (!ix || index_bv_count(*ix) == 0 || ix->bvs.size() != index_bv_count(*ix)) continue;
+        if (hipMalloc(&d_keys[x].p, ix->keys.size() * 8) != hipSuccess ||
+            hipMalloc(&d_bvs[x].p, ix->bvs.size() * sizeof(uint64_t*)) != hipSuccess)
+            return fail(CUBIT_ERR_OOM, "merge index descriptor allocation failed");
+        HIP_CHECK(hipMemcpyAsync(d_keys[x].p, ix->keys.data(), ix->keys.size() * 8, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_bvs[x].p, ix->bvs.data(), ix->bvs.size() * sizeof(uint64_t*), hipMemcpyHostToDevice, s));
+        mi[x].keys = static_cast<const int64_t*>(d_keys[x].p);
+        mi[x].bvs = static_cast<uint64_t* const*>(d_bvs[x].p);
+        mi[x].n_keys = (uint32_t)ix->keys.size();
+        mi[x].encoding = ix->encoding == CUBIT_INDEX_RANGE ? 0 : ix->encoding == CUBIT_INDEX_EQUALITY ? 1 : 2;
+    }
+    // every 64-row word holding merged rows, rewritten by one wave (rows ascend, each once)
+    // FLOAT / DOUBLE: the merge compares and writes keys (the key column is what the indexes were built
+    // from); the patterns are scattered into the pattern column beside it
+    DevBuf d_keys_of;
+    const int64_t* merge_vals = vals_p;
+    if (type_is_fp(c.type)) {
+        if (hipMalloc(&d_keys_of.p, m * 8) != hipSuccess) return fail(CUBIT_ERR_OOM, "merge key allocation failed");
+        HIP_CHECK(launch_value_keys(vals_p, m, c.type, static_cast<int64_t*>(d_keys_of.p), s));
+        merge_vals = static_cast<const int64_t*>(d_keys_of.p);
+    }
+    HIP_CHECK(launch_merge_words(rows_p, merge_vals, valid_p, m, t->n_rows, const_cast<void*>(c.data), ktype(c),
+                                 const_cast<uint64_t*>(c.validity), mi[0], mi[1], s));
+    if (type_is_fp(c.type))
+        HIP_CHECK(launch_scatter_raw(rows_p, vals_p, valid_p, m, c.type, const_cast<void*>(c.raw), s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    // statistics and exact keys for the merged values (a merged NULL leaves the index bounds:
+    // they only have to contain the valid values)
+    for (Index* ix : ixs) {
+        if (!ix || added.empty()) continue;
+        const bool was_empty = ix->empty;
+        const int64_t old_min = ix->vmin;
+        ix->vmin = was_empty ? added.front() : std::min(ix->vmin, added.front());
+        ix->vmax = was_empty ? added.back() : std::max(ix->vmax, added.back());
+        ix->empty = false;
+        if (int rc = maintain_exact_keys(t, col, *ix, added, old_min, was_empty)) return rc;
+    }
+    return CUBIT_OK;
+}
+
+}  // namespace
+
 // Merge committed updates of one column into its base values and indexes (the checkpoint of
 // update chains; CUBIT folds its update bitvectors into the index the same way). Every record
 // with version < horizon — visible to every snapshot the caller still serves (start_time ≥
@@ -2969,12 +3039,6 @@ extern "C" int cubit_table_merge_updates(cubit_table* t, int col, uint64_t horiz
     if (c.type == CUBIT_TYPE_INT32 && !added.empty() && (added.front() < INT32_MIN || added.back() > INT32_MAX))
         return fail(CUBIT_ERR_INVALID, "merged value %lld does not fit an INT32 column",
                     (long long)(added.front() < INT32_MIN ? added.front() : added.back()));
-    HIP_CHECK(hipStreamSynchronize(s));
-    drop_zones(t);  // the merge rewrites index words in place
-    if (int rc = own_column(t, c, std::max<uint64_t>(t->n_rows, c.cap_rows))) return rc;
-    if (m_null)
-        if (int rc = ensure_validity(t, c)) return rc;
-    c.drop_packed();  // merged values are not in the segments
     DevBuf d_rows, d_vals, d_valid;
     const int64_t* rows_p;
     const int64_t* vals_p;
@@ -2994,48 +3058,7 @@ extern "C" int cubit_table_merge_updates(cubit_table* t, int col, uint64_t horiz
         vals_p = static_cast<const int64_t*>(d_vals.p);
         valid_p = m_null ? static_cast<const uint8_t*>(d_valid.p) : nullptr;
     }
-    Index* ixs[2] = {t->idx.count(col) ? &t->idx[col] : nullptr, t->bins.count(col) ? &t->bins[col] : nullptr};
-    MergeIndex mi[2] = {};
-    DevBuf d_keys[2], d_bvs[2];
-    for (int x = 0; x < 2; ++x) {
-        Index* ix = ixs[x];
-        if (!ix || index_bv_count(*ix) == 0 || ix->bvs.size() != index_bv_count(*ix)) continue;
-        if (hipMalloc(&d_keys[x].p, ix->keys.size() * 8) != hipSuccess ||
-            hipMalloc(&d_bvs[x].p, ix->bvs.size() * sizeof(uint64_t*)) != hipSuccess)
-            return fail(CUBIT_ERR_OOM, "merge index descriptor allocation failed");
-        HIP_CHECK(hipMemcpyAsync(d_keys[x].p, ix->keys.data(), ix->keys.size() * 8, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(d_bvs[x].p, ix->bvs.data(), ix->bvs.size() * sizeof(uint64_t*), hipMemcpyHostToDevice, s));
-        mi[x].keys = static_cast<const int64_t*>(d_keys[x].p);
-        mi[x].bvs = static_cast<uint64_t* const*>(d_bvs[x].p);
-        mi[x].n_keys = (uint32_t)ix->keys.size();
-        mi[x].encoding = ix->encoding == CUBIT_INDEX_RANGE ? 0 : ix->encoding == CUBIT_INDEX_EQUALITY ? 1 : 2;
-    }
-    // every 64-row word holding merged rows, rewritten by one wave (rows ascend, each once)
-    // FLOAT / DOUBLE: the merge compares and writes keys (the key column is what the indexes were built
-    // from); the patterns are scattered into the pattern column beside it
-    DevBuf d_keys_of;
-    const int64_t* merge_vals = vals_p;
-    if (type_is_fp(c.type)) {
-        if (hipMalloc(&d_keys_of.p, m * 8) != hipSuccess) return fail(CUBIT_ERR_OOM, "merge key allocation failed");
-        HIP_CHECK(launch_value_keys(vals_p, m, c.type, static_cast<int64_t*>(d_keys_of.p), s));
-        merge_vals = static_cast<const int64_t*>(d_keys_of.p);
-    }
-    HIP_CHECK(launch_merge_words(rows_p, merge_vals, valid_p, m, t->n_rows, const_cast<void*>(c.data), ktype(c),
-                                 const_cast<uint64_t*>(c.validity), mi[0], mi[1], s));
-    if (type_is_fp(c.type))
-        HIP_CHECK(launch_scatter_raw(rows_p, vals_p, valid_p, m, c.type, const_cast<void*>(c.raw), s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    // statistics and exact keys for the merged values (a merged NULL leaves the index bounds:
-    // they only have to contain the valid values)
-    for (Index* ix : ixs) {
-        if (!ix || added.empty()) continue;
-        const bool was_empty = ix->empty;
-        const int64_t old_min = ix->vmin;
-        ix->vmin = was_empty ? added.front() : std::min(ix->vmin, added.front());
-        ix->vmax = was_empty ? added.back() : std::max(ix->vmax, added.back());
-        ix->empty = false;
-        if (int rc = maintain_exact_keys(t, col, *ix, added, old_min, was_empty)) return rc;
-    }
+    if (int rc = apply_records(t, col, c, rows_p, vals_p, valid_p, m, added, m_null)) return rc;
     // the records left (each row's suffix at or past horizon), still grouped and chronological
     if (k_rows.empty()) {
         t->upd.erase(col);
@@ -3045,6 +3068,130 @@ extern "C" int cubit_table_merge_updates(cubit_table* t, int col, uint64_t horiz
     }
     drop_derived(t);
     if (n_merged) *n_merged = m;
+    return CUBIT_OK;
+}
+
+// Bring one column to new contents given whole (what a host engine holds after committed UPDATEs:
+// the values, with no list of the rows that changed). The changed rows are found on the device —
+// column_diff_kernel over the old and the new column and validity, one "changed" bitvector and its
+// count — decoded into ascending row ids by the ordered decode, their new values gathered
+// (sync_gather_kernel), and the records go through the merge's second half (apply_records). More
+// than max_changed changed rows: nothing is touched and *applied = 0 (the caller rebuilds).
+// Device memory beside the table while the call runs: the staged column and validity for host
+// input (n_rows × element size + nwp × 8 bytes; none with on_device), the changed bitvector
+// (nwp × 8) and 17 bytes per changed row (row id, value, valid flag; 25 for FLOAT / DOUBLE).
+extern "C" int cubit_table_sync_column(cubit_table* t, int col, const void* values, const uint64_t* validity,
+                                       int on_device, uint64_t max_changed, uint64_t* n_changed, int* applied) {
+    if (!t || !n_changed || !applied) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    auto cit = t->cols.find(col);
+    if (cit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column %d not registered", col);
+    auto uit = t->upd.find(col);
+    if (uit != t->upd.end() && uit->second.n)
+        return fail(CUBIT_ERR_INVALID, "column %d has %llu update records outstanding (merge or clear them first)", col,
+                    (unsigned long long)uit->second.n);
+    const uint64_t n = t->n_rows;
+    if (n == 0) {
+        *n_changed = 0;
+        *applied = 1;
+        return CUBIT_OK;
+    }
+    if (!values) return fail(CUBIT_ERR_INVALID, "null values");
+    if (int rc = set_device(t->ctx)) return rc;
+    hipStream_t s = t->ctx->stream;
+    Column& c = cit->second;
+    const uint64_t esz = type_is32(c.type) ? 4 : 8, n_words = (n + 63) / 64, nwp = padded_words(n);
+    // 1. the new contents on the device: read in place, or staged
+    DevBuf st_col, st_valid, d_changed, d_cnt;
+    const void* new_col = values;
+    const uint64_t* new_valid = validity;
+    if (hipMalloc(&d_changed.p, nwp * 8) != hipSuccess || hipMalloc(&d_cnt.p, 16) != hipSuccess)
+        return fail(CUBIT_ERR_OOM, "sync bitvector allocation failed");
+    const bool tm = sync_timing();
+    uint64_t ns[5] = {tm ? now_ns() : 0, 0, 0, 0, 0};
+    if (!on_device) {
+        if (hipMalloc(&st_col.p, std::max<uint64_t>(n * esz, 16)) != hipSuccess ||
+            (validity && hipMalloc(&st_valid.p, n_words * 8) != hipSuccess))
+            return fail(CUBIT_ERR_OOM, "sync staging allocation of %llu bytes failed",
+                        (unsigned long long)(n * esz + (validity ? n_words * 8 : 0)));
+        HIP_CHECK(hipMemcpyAsync(st_col.p, values, n * esz, hipMemcpyHostToDevice, s));
+        if (validity) HIP_CHECK(hipMemcpyAsync(st_valid.p, validity, n_words * 8, hipMemcpyHostToDevice, s));
+        new_col = st_col.p;
+        new_valid = validity ? static_cast<const uint64_t*>(st_valid.p) : nullptr;
+    }
+    if (tm) {
+        HIP_CHECK(hipStreamSynchronize(s));  // the staging copies
+        ns[1] = now_ns();
+    }
+    // 2. the diff: one pass, the changed bitvector and its count (a timed launch with timing on)
+    HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 16, s));
+    hipEvent_t e0, e1;
+    if (int rc = timing_events(t->ctx, e0, e1)) return rc;
+    HIP_CHECK(launch_column_diff(raw_of(c), c.validity, new_col, new_valid, c.type, n, static_cast<uint64_t*>(d_changed.p),
+                                 static_cast<uint64_t*>(d_cnt.p), s, e0, e1));
+    uint64_t m = 0;
+    HIP_CHECK(hipMemcpyAsync(&m, d_cnt.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (tm) {
+        ns[2] = now_ns();
+        std::fprintf(stderr, "cubit sync timing: %llu rows, %llu changed: staging + H2D %.2f ms, diff %.2f ms\n",
+                     (unsigned long long)n, (unsigned long long)m, (ns[1] - ns[0]) * 1e-6, (ns[2] - ns[1]) * 1e-6);
+    }
+    *n_changed = m;
+    if (m > max_changed) {
+        *applied = 0;
+        return CUBIT_OK;
+    }
+    *applied = 1;
+    if (m == 0) return CUBIT_OK;  // nothing written: zone maps and patched leaves stand
+    // 3. the changed rows as records: ascending local ids (the ordered decode of the one leaf),
+    //    then their new values and NULL-ness
+    DevBuf d_rows, d_vals, d_valid;
+    if (hipMalloc(&d_rows.p, m * 8) != hipSuccess || hipMalloc(&d_vals.p, m * 8) != hipSuccess ||
+        hipMalloc(&d_valid.p, m) != hipSuccess)
+        return fail(CUBIT_ERR_OOM, "sync record list allocation failed");
+    EvalProgram prog{};
+    prog.leaf[0] = static_cast<const uint64_t*>(d_changed.p);
+    prog.n_leaves = 1;
+    uint64_t* d_decoded = static_cast<uint64_t*>(d_cnt.p) + 1;
+    if (int rc = run_eval(t->ctx, prog, n, 0, static_cast<int64_t*>(d_rows.p), m, d_decoded, nullptr, RunMode::kDecode,
+                          false, true))
+        return rc;
+    HIP_CHECK(launch_sync_gather(new_col, new_valid, c.type, static_cast<const int64_t*>(d_rows.p), m,
+                                 static_cast<int64_t*>(d_vals.p), static_cast<uint8_t*>(d_valid.p), s));
+    std::unique_ptr<int64_t[]> h_vals(new int64_t[m]);  // not zeroed: the copy fills it
+    std::vector<uint8_t> h_valid;
+    if (new_valid) h_valid.resize(m);
+    uint64_t decoded = 0;
+    HIP_CHECK(hipMemcpyAsync(&decoded, d_decoded, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(h_vals.get(), d_vals.p, m * 8, hipMemcpyDeviceToHost, s));
+    if (new_valid) HIP_CHECK(hipMemcpyAsync(h_valid.data(), d_valid.p, m, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (decoded != m)
+        return fail(CUBIT_ERR_HIP, "sync decoded %llu changed rows, the diff counted %llu", (unsigned long long)decoded,
+                    (unsigned long long)m);
+    if (int rc = check_codes(c, h_vals.get(), new_valid ? h_valid.data() : nullptr, m)) return rc;
+    // the records' distinct valid values as keys (compacted in place): the statistics and exact
+    // keys they add
+    uint64_t n_valid = m;
+    if (new_valid || type_is_keyed(c.type)) {
+        n_valid = 0;
+        for (uint64_t i = 0; i < m; ++i)
+            if (!new_valid || h_valid[i]) h_vals[n_valid++] = value_key(c.type, h_vals[i]);
+    }
+    const bool any_null = n_valid < m;
+    const std::vector<int64_t> added = distinct_sorted(h_vals.get(), n_valid);
+    if (tm) ns[3] = now_ns();
+    // 4. the merge's second half
+    if (int rc = apply_records(t, col, c, static_cast<const int64_t*>(d_rows.p), static_cast<const int64_t*>(d_vals.p),
+                               new_valid ? static_cast<const uint8_t*>(d_valid.p) : nullptr, m, added, any_null))
+        return rc;
+    drop_derived(t);
+    if (tm) {
+        ns[4] = now_ns();
+        std::fprintf(stderr, "cubit sync timing: decode + gather + records to host %.2f ms, merge %.2f ms\n",
+                     (ns[3] - ns[2]) * 1e-6, (ns[4] - ns[3]) * 1e-6);
+    }
     return CUBIT_OK;
 }
 

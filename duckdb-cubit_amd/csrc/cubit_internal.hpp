@@ -329,4 +329,18 @@ hipError_t launch_splice_bits(uint64_t* dst, const uint64_t* src, uint64_t bit_o
 hipError_t launch_merge_words(const int64_t* rows, const int64_t* values, const uint8_t* valids, uint64_t m,
                               uint64_t n_rows, void* col, int type, uint64_t* validity, MergeIndex ix0, MergeIndex ix1,
                               hipStream_t stream);
+// Column sync: changed[w] = the rows of word w whose NULL-ness differs between the old and the new
+// column, or that are valid on both sides with different stored bits (`type` gives the element
+// size only; FLOAT / DOUBLE callers pass the pattern column). changed holds padded_words(n_rows)
+// words, all written (0 past the rows); the changed rows are added into *counter (zeroed by the
+// caller). The validities may be null (all valid) and are read only below ceil(n_rows / 64) words.
+// ev0 / ev1 (optional) are stamped by the dispatch, as for launch_eval_decode.
+hipError_t launch_column_diff(const void* old_col, const uint64_t* old_valid, const void* new_col,
+                              const uint64_t* new_valid, int type, uint64_t n_rows, uint64_t* changed,
+                              uint64_t* counter, hipStream_t stream, hipEvent_t ev0 = nullptr,
+                              hipEvent_t ev1 = nullptr);
+// the records of m changed rows (ascending local ids) as launch_merge_words takes them: values[i] =
+// the new column at rows[i] (INT32 / codes sign-extended, FLOAT zero-extended, 0 for NULL), valids[i]
+hipError_t launch_sync_gather(const void* new_col, const uint64_t* new_valid, int type, const int64_t* rows, uint64_t m,
+                              int64_t* values, uint8_t* valids, hipStream_t stream);
 }  // namespace cubit

@@ -3244,6 +3244,87 @@ __global__ __launch_bounds__(256) void update_mask_kernel(const int64_t* __restr
     }
 }
 
+// Column sync (cubit_table_sync_column): which rows of a column differ from the new contents a
+// host engine holds after committed UPDATEs. One streaming pass over the old values, the old
+// validity, the new values and the new validity, in the layout of compare_bitvectors_kernel: a
+// wave handles 64 consecutive words, lane l reads row l of each word (one coalesced 256- / 512-byte
+// load per word and side, 8 words of both sides loaded ahead), the word's "changed" mask is one
+// ballot kept by lane j for word j, and the 64 masks leave as one 512-byte plain store. A row
+// changed when its NULL-ness differs, or when it is valid on both sides and the stored bits
+// differ (FLOAT / DOUBLE: the caller passes the pattern column, so -0.0 → +0.0 is a change); two
+// NULLs are equal whatever their slots hold. Rows past n_rows never count and the padding words
+// up to n_words_padded are written as 0. The changed rows are counted from the masks: per lane,
+// then per wave, then per workgroup (LDS, 4 words), one atomicAdd per workgroup into *counter.
+// old_valid / new_valid may be null (every row valid); both are read only below n_words.
+// Bytes per pass: n · 2 · sizeof(T) + 3 · n / 8.
+template <typename T>
+__global__ __launch_bounds__(256) void column_diff_kernel(const T* __restrict__ old_col,
+                                                          const uint64_t* __restrict__ old_valid,
+                                                          const T* __restrict__ new_col,
+                                                          const uint64_t* __restrict__ new_valid, uint64_t n_rows,
+                                                          uint64_t n_words, uint64_t n_words_padded,
+                                                          uint64_t* __restrict__ changed,
+                                                          unsigned long long* __restrict__ counter) {
+    constexpr int JB = 8;
+    __shared__ uint64_t s_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t wave_id = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    uint64_t cnt = 0;
+    for (uint64_t w0 = wave_id * 64; w0 < n_words_padded; w0 += n_waves * 64) {
+        uint64_t mine = 0;  // lane j keeps word w0 + j
+        if (w0 < n_words) {  // a wave wholly in the padding stores zeros
+            for (int jb = 0; jb < 64; jb += JB) {
+                T a[JB], b[JB];
+                uint64_t va[JB], vb[JB];
+                bool in[JB];
+#pragma unroll
+                for (int j = 0; j < JB; ++j) {
+                    const uint64_t w = w0 + jb + j, row = w * 64 + lane;
+                    in[j] = row < n_rows;
+                    a[j] = in[j] ? __builtin_nontemporal_load(old_col + row) : (T)0;  // streamed once: nt
+                    b[j] = in[j] ? __builtin_nontemporal_load(new_col + row) : (T)0;
+                    va[j] = old_valid && w < n_words ? old_valid[w] : ~0ull;
+                    vb[j] = new_valid && w < n_words ? new_valid[w] : ~0ull;
+                }
+#pragma unroll
+                for (int j = 0; j < JB; ++j) {
+                    const bool oa = (va[j] >> lane) & 1ull, ob = (vb[j] >> lane) & 1ull;
+                    const uint64_t m = __ballot(in[j] && (oa != ob || (oa && a[j] != b[j])));
+                    if (lane == jb + j) mine = m;
+                }
+            }
+        }
+        changed[w0 + lane] = mine;
+        cnt += (uint64_t)__popcll(mine);
+    }
+    cnt = wave_sum(cnt);
+    if (lane == 0) s_cnt[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint64_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (total) atomicAdd(counter, (unsigned long long)total);
+    }
+}
+
+// The changed rows' records for merge_words_kernel, read from the new column and validity at the
+// ascending row ids the ordered decode produced: values[i] as the ABI carries a value (INT32 and
+// codes sign-extended, a FLOAT pattern zero-extended, 0 for a NULL record) and valids[i] (1 = the
+// value, 0 = NULL).
+template <typename T>
+__global__ __launch_bounds__(256) void sync_gather_kernel(const T* __restrict__ new_col,
+                                                          const uint64_t* __restrict__ new_valid,
+                                                          const int64_t* __restrict__ rows, uint64_t m,
+                                                          int64_t* __restrict__ values, uint8_t* __restrict__ valids) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) {
+        const uint64_t r = (uint64_t)rows[i];
+        const bool ok = !new_valid || ((new_valid[r >> 6] >> (r & 63)) & 1ull);
+        values[i] = ok ? (int64_t)new_col[r] : 0;
+        valids[i] = ok ? 1 : 0;
+    }
+}
+
 unsigned grid_for(uint64_t n, unsigned cap = 4096) {
     const uint64_t b = (n + 255) / 256;
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(b, cap));
@@ -4058,6 +4139,40 @@ hipError_t launch_merge_words(const int64_t* rows, const int64_t* values, const 
     if (m == 0) return hipSuccess;
     hipLaunchKernelGGL(merge_words_kernel, dim3(grid_for(m)), dim3(256), 0, stream, rows, values, valids, m,
                        n_rows, col, type, validity, ix0, ix1);
+    return hipGetLastError();
+}
+
+hipError_t launch_column_diff(const void* old_col, const uint64_t* old_valid, const void* new_col,
+                              const uint64_t* new_valid, int type, uint64_t n_rows, uint64_t* changed,
+                              uint64_t* counter, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+    const uint64_t nw = padded_words(n_rows), n_words = (n_rows + 63) / 64;
+    // the compare kernel's grid: four waves per workgroup, a wave per 64 words
+    const dim3 grid((unsigned)std::max<uint64_t>(std::min<uint64_t>((nw / 64 + 3) / 4, 8192), 1)), block(256);
+    auto* cnt = reinterpret_cast<unsigned long long*>(counter);
+    if (type_is32(type))
+        hipExtLaunchKernelGGL(column_diff_kernel<uint32_t>, grid, block, 0, stream, ev0, ev1, 0,
+                              static_cast<const uint32_t*>(old_col), old_valid, static_cast<const uint32_t*>(new_col),
+                              new_valid, n_rows, n_words, nw, changed, cnt);
+    else
+        hipExtLaunchKernelGGL(column_diff_kernel<uint64_t>, grid, block, 0, stream, ev0, ev1, 0,
+                              static_cast<const uint64_t*>(old_col), old_valid, static_cast<const uint64_t*>(new_col),
+                              new_valid, n_rows, n_words, nw, changed, cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_sync_gather(const void* new_col, const uint64_t* new_valid, int type, const int64_t* rows, uint64_t m,
+                              int64_t* values, uint8_t* valids, hipStream_t stream) {
+    if (m == 0) return hipSuccess;
+    const dim3 grid(grid_for(m)), block(256);
+    if (type == kTypeFloat)  // the pattern zero-extended, as the probe hands it back
+        hipLaunchKernelGGL(sync_gather_kernel<uint32_t>, grid, block, 0, stream, static_cast<const uint32_t*>(new_col),
+                           new_valid, rows, m, values, valids);
+    else if (type_is32(type))
+        hipLaunchKernelGGL(sync_gather_kernel<int32_t>, grid, block, 0, stream, static_cast<const int32_t*>(new_col),
+                           new_valid, rows, m, values, valids);
+    else
+        hipLaunchKernelGGL(sync_gather_kernel<int64_t>, grid, block, 0, stream, static_cast<const int64_t*>(new_col),
+                           new_valid, rows, m, values, valids);
     return hipGetLastError();
 }
 

@@ -193,6 +193,7 @@ GPU_SIGNATURES = {
     "cubit_host_free": (C.c_int, [_P, _P]),
     "cubit_ctx_last_decode_kernel": (C.c_int, [_P, _P]),
     "cubit_table_merge_updates": (C.c_int, [_P, C.c_int, _U64, _P]),
+    "cubit_table_sync_column": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _U64, C.POINTER(_U64), C.POINTER(C.c_int)]),
     "cubit_table_save_index": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p]),
     "cubit_table_load_index": (C.c_int, [_P, C.c_int, C.c_char_p]),
 }

@@ -461,6 +461,44 @@ class CubitTable:
         L.check(self.lib.cubit_table_merge_updates(self.handle, col, int(horizon), C.byref(n)))
         return int(n.value)
 
+    def sync_column(self, col: int, data, validity=None, max_changed: Optional[int] = None,
+                    on_device: bool = False) -> Tuple[int, bool]:
+        """Bring `col` to new contents given whole (cubit_table_sync_column): the changed rows are
+        found on the GPU and merged into the base and every index of the column. data = n_rows
+        values of the column's dtype (as append takes them), validity = LSB-first words or None
+        (all valid); or, for the on-device form, DeviceBuffers / device addresses holding the
+        same. max_changed = None means n_rows. Returns (n_changed, applied); applied False = more
+        than max_changed rows changed and nothing was touched."""
+        def dev_addr(x):
+            return x.addr if isinstance(x, DeviceBuffer) else int(x)
+
+        keep = []
+        if isinstance(data, DeviceBuffer) or isinstance(data, int) or on_device:
+            on_device = True
+            dptr = dev_addr(data)
+            vptr = None if validity is None else dev_addr(validity)
+        else:
+            a = np.ascontiguousarray(data)
+            want = {L.TYPE_INT32: np.int32, L.TYPE_FLOAT: np.float32, L.TYPE_DOUBLE: np.float64,
+                    L.TYPE_VARCHAR: np.int32, L.TYPE_UINT64: np.uint64}.get(self.types.get(col), np.int64)
+            if col in self.types and (a.dtype != want or len(a) != self.n_rows):
+                raise ValueError(f"column {col}: {len(a)} values of {a.dtype}, want {self.n_rows} of {np.dtype(want)}")
+            keep.append(a)
+            dptr = a.ctypes.data
+            vptr = None
+            if validity is not None:
+                v = np.ascontiguousarray(validity, dtype=np.uint64)
+                if len(v) < (self.n_rows + 63) // 64:
+                    raise ValueError(f"column {col}: {len(v)} validity words for {self.n_rows} rows")
+                keep.append(v)
+                vptr = v.ctypes.data
+        n, applied = C.c_uint64(), C.c_int()
+        L.check(self.lib.cubit_table_sync_column(self.handle, col, C.c_void_p(dptr), C.c_void_p(vptr) if vptr else None,
+                                                 1 if on_device else 0,
+                                                 self.n_rows if max_changed is None else int(max_changed),
+                                                 C.byref(n), C.byref(applied)))
+        return int(n.value), bool(applied.value)
+
     # ------------------------------------------------------------------ scan
     def scan_into(self, plan_nodes, rowids_dptr: int, capacity: int, count_dptr: int,
                   txn: Optional[L.Txn] = None, count_only: bool = False, ordered: bool = False,

@@ -1404,11 +1404,62 @@ static void SetDeletes(CubitPartitionSet &set, const vector<bool> &present, uint
     }
 }
 
+// After a committed UPDATE of an attached column: every partition's columns brought to the
+// snapshot's values in place (cubit_table_sync_column: the changed rows are found on the GPU and
+// merged into the base values and every index), rows [0, gpu_rows) sliced by partition. A row the
+// snapshot lacks (deleted) reads as NULL there, as a rebuild would store it; it is invisible
+// either way (SetDeletes). False when a partition reports more changed rows than the plan allows
+// (applied = 0): the caller rebuilds, which replaces the set, so what was applied before does not
+// matter. Holds the set's rw exclusively; no scan is admitted to the set before the sync
+// publishes, as the folded writers stay recorded until then.
+static bool SyncColumns(CubitPartitionSet &cur, CubitAttached &attached, const CubitSnapshot &snap, uint64_t gpu_rows,
+                        const core::UpdateSyncPlan &plan) {
+    lock_guard<mutex> g(attached.lock);
+    std::unique_lock<std::shared_mutex> writing(cur.rw);
+    for (idx_t c = 0; c < attached.column_order.size(); c++) {
+        const column_t col = attached.column_order[c];
+        const auto traits = Traits(attached.columns[col]);
+        vector<int32_t> narrow;
+        const char *data = nullptr;
+        if (traits.dict) {  // codes in the kept dictionary (every valid string is in it: the caller checked)
+            vector<char> bytes;
+            vector<uint64_t> offsets;
+            PackStrings(snap.strings[c], bytes, offsets);
+            narrow.assign(snap.rows, 0);
+            Check(cubit_dict_encode(cur.dicts.at(col), bytes.data(), offsets.data(), snap.rows, snap.validity[c].data(),
+                                    narrow.data()));
+            data = reinterpret_cast<const char *>(narrow.data());
+        } else if (traits.wide) {
+            data = reinterpret_cast<const char *>(snap.values[c].data());
+        } else {
+            narrow.assign(snap.values[c].begin(), snap.values[c].begin() + gpu_rows);
+            data = reinterpret_cast<const char *>(narrow.data());
+        }
+        const uint64_t esz = traits.wide ? 8 : 4;
+        for (size_t p = 0; p < cur.parts.size(); p++) {
+            // partition boundaries are whole row groups, so its validity words are the snapshot's own
+            const uint64_t b = cur.part_base[p], e = p + 1 < cur.parts.size() ? cur.part_base[p + 1] : gpu_rows;
+            uint64_t n_changed = 0;
+            int applied = 0;
+            Check(cubit_table_sync_column(cur.parts[p], (int)col, data + b * esz, snap.validity[c].data() + b / 64, 0,
+                                          plan.MaxChanged(e - b), &n_changed, &applied));
+            if (!applied) {
+                return false;
+            }
+        }
+    }
+    return true;
+}
+
 // Bring the partition to the table's committed state, reading every attached column in one
 // transaction (so no commit lands between two columns). Appends only: the new row ids are
-// read and appended (cubit_table_append, every index maintained in place); after an UPDATE of
-// an attached column, or when row ids shrank (a checkpoint's vacuum renumbers them), every
-// column is read again. Row ids the snapshot lacks are deletes, committed before it began.
+// read and appended (cubit_table_append, every index maintained in place). After an UPDATE of
+// an attached column every column is read again and synced in place (SyncColumns: the GPU finds
+// the changed rows and merges them, core::PlanUpdateSync decides whether and up to how many), the
+// rows past the partition appended as usual; the partition set is rebuilt instead when more rows
+// changed than the plan allows, when a dictionary column gained a string, or when row ids shrank
+// (a checkpoint's vacuum renumbers them). Row ids the snapshot lacks are deletes, committed
+// before it began.
 static void SyncPartition(ClientContext &context, DuckTableEntry &entry, CubitAttached &attached,
                           const string &table_name, bool rebuild) {
     // the caller holds attached.sync_lock: syncs and attaches of this table run one at a time
@@ -1424,6 +1475,7 @@ static void SyncPartition(ClientContext &context, DuckTableEntry &entry, CubitAt
     vector<transaction_t> folded;
     std::shared_ptr<CubitPartitionSet> cur;
     uint64_t gpu_rows = 0;
+    bool updated = false;  // a folded writer updated an attached column
     {
         lock_guard<mutex> g(attached.lock);
         // writers that were active before this sync and may commit after its snapshot: those
@@ -1435,7 +1487,7 @@ static void SyncPartition(ClientContext &context, DuckTableEntry &entry, CubitAt
         for (auto &w : attached.writers) {
             if (w.first < lowest_active) {
                 folded.push_back(w.first);
-                rebuild |= w.second;
+                updated |= w.second;
             }
         }
         if (attached.Attached()) {
@@ -1454,9 +1506,29 @@ static void SyncPartition(ClientContext &context, DuckTableEntry &entry, CubitAt
         }
         attached.sync_start = start;
     };
-    CubitSnapshot snap;
+    CubitSnapshot snap, tail;
     vector<bool> present;  // presence of every row id of the table in this snapshot
-    if (!rebuild && cur) {
+    bool full = false;     // snap holds every row id from 0
+    bool synced = false;   // the partitions' columns were brought to snap in place
+    if (!rebuild && updated && cur) {
+        ReadRows(con, table_name, entry, attached.column_order, 0, total_rows, snap);
+        full = true;
+        bool new_string = false;
+        for (idx_t c = 0; c < attached.column_order.size() && !new_string; c++) {
+            auto d = cur->dicts.find(attached.column_order[c]);
+            new_string = d != cur->dicts.end() && !StringsInDict(d->second, snap.strings[c], snap.validity[c]);
+        }
+        const bool shrank = entry.GetStorage().GetTotalRows() < gpu_rows || snap.rows < gpu_rows;
+        const auto plan = core::PlanUpdateSync(gpu_rows, snap.rows, shrank, new_string, core::kDefaultSyncChangedFraction);
+        if (plan.in_place) {
+            if (snap.rows > gpu_rows) {  // the rows past the partition, appended below as after any sync
+                ReadRows(con, table_name, entry, attached.column_order, gpu_rows, total_rows, tail);
+            }
+            synced = SyncColumns(*cur, attached, snap, gpu_rows, plan);
+        }
+    }
+    rebuild |= updated && !synced;
+    if (!rebuild && cur && !synced) {
         // rows appended since the partition was read, then which older rows remain
         ReadRows(con, table_name, entry, attached.column_order, gpu_rows, total_rows, snap);
         auto res = con.Query("SELECT rowid FROM " + KeywordHelper::WriteOptionallyQuoted(table_name) +
@@ -1483,7 +1555,9 @@ static void SyncPartition(ClientContext &context, DuckTableEntry &entry, CubitAt
         }
     }
     if (rebuild || !cur) {
-        ReadRows(con, table_name, entry, attached.column_order, 0, total_rows, snap);
+        if (!full) {
+            ReadRows(con, table_name, entry, attached.column_order, 0, total_rows, snap);
+        }
         if (snap.rows == 0) {
             con.Commit();
             throw InvalidInputException("cubit: %s has no rows to attach", table_name);
@@ -1504,7 +1578,11 @@ static void SyncPartition(ClientContext &context, DuckTableEntry &entry, CubitAt
     // meanwhile (the set's rw, exclusive) and none is admitted before the new state is published
     lock_guard<mutex> g(attached.lock);
     std::unique_lock<std::shared_mutex> writing(cur->rw);
-    if (snap.rows) {
+    const CubitSnapshot &app = synced ? tail : snap;  // the rows to append
+    if (synced) {
+        present.assign(snap.present.begin(), snap.present.begin() + gpu_rows);
+    }
+    if (app.rows) {
         vector<int> cols;
         vector<const void *> data;
         vector<const uint64_t *> valid;
@@ -1516,23 +1594,23 @@ static void SyncPartition(ClientContext &context, DuckTableEntry &entry, CubitAt
             if (Traits(attached.columns[col]).dict) {  // codes in the kept dictionary
                 vector<char> bytes;
                 vector<uint64_t> offsets;
-                PackStrings(snap.strings[c], bytes, offsets);
-                narrow.emplace_back(snap.rows, 0);
-                Check(cubit_dict_encode(cur->dicts.at(col), bytes.data(), offsets.data(), snap.rows,
-                                        snap.validity[c].data(), narrow.back().data()));
+                PackStrings(app.strings[c], bytes, offsets);
+                narrow.emplace_back(app.rows, 0);
+                Check(cubit_dict_encode(cur->dicts.at(col), bytes.data(), offsets.data(), app.rows,
+                                        app.validity[c].data(), narrow.back().data()));
                 data.push_back(narrow.back().data());
             } else if (Traits(attached.columns[col]).wide) {
-                data.push_back(snap.values[c].data());
+                data.push_back(app.values[c].data());
             } else {
-                narrow.emplace_back(snap.values[c].begin(), snap.values[c].end());
+                narrow.emplace_back(app.values[c].begin(), app.values[c].end());
                 data.push_back(narrow.back().data());
             }
-            valid.push_back(snap.validity[c].data());
+            valid.push_back(app.validity[c].data());
         }
-        Check(cubit_table_append(cur->parts.back(), snap.rows, cols.data(), data.data(), valid.data(),
+        Check(cubit_table_append(cur->parts.back(), app.rows, cols.data(), data.data(), valid.data(),
                                  (uint32_t)cols.size(), 0));
-        gpu_rows += snap.rows;
-        present.insert(present.end(), snap.present.begin(), snap.present.end());
+        gpu_rows += app.rows;
+        present.insert(present.end(), app.present.begin(), app.present.end());
     }
     SetDeletes(*cur, present, gpu_rows);
     attached.gpu_rows = gpu_rows;

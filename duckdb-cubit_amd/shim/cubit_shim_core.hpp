@@ -311,6 +311,40 @@ inline std::vector<std::vector<int64_t>> LocalDeletes(const std::vector<bool> &p
     return local;
 }
 
+// ------------------------------------------------------------------ update sync
+
+// After a committed UPDATE of an attached column the shim holds the column's new contents and no
+// list of the changed rows. cubit_table_sync_column finds them on the GPU and merges them in
+// place, as long as few enough rows changed; past that a rebuild of the partition set is cheaper.
+// The changed-row fraction up to which the sync is tried: measured (scripts/sync_timing.py, 612 M
+// rows, DESIGN.md §7 has the numbers) — at 1 % the host-form sync takes 0.5-1.2 of a rebuild of the
+// column, at 10 % 1.4-3.3 of it.
+static constexpr double kDefaultSyncChangedFraction = 0.01;
+
+// Whether an update sync may run in place: the partition set holds rows (part_rows > 0), the
+// snapshot covers every one of them (snap_rows >= part_rows: the rows past them are appended as
+// usual), row ids did not shrink (a vacuum renumbers them: every row may differ) and no dictionary
+// column gained a string (the partitions keep their dictionary). The fraction does not decide
+// this: with a fraction of 0 (or below, or NaN) the sync still runs and applies only when no row
+// changed. When any partition reports applied = 0 the caller rebuilds.
+struct UpdateSyncPlan {
+    bool in_place;    // false: rebuild
+    double fraction;  // the changed-row fraction, clamped to [0, 1]
+    // max_changed of cubit_table_sync_column for a partition of `rows` rows: floor(fraction × rows),
+    // never above the rows
+    uint64_t MaxChanged(uint64_t rows) const {
+        if (fraction >= 1.0) {
+            return rows;
+        }
+        return std::min((uint64_t)((long double)fraction * (long double)rows), rows);
+    }
+};
+inline UpdateSyncPlan PlanUpdateSync(uint64_t part_rows, uint64_t snap_rows, bool ids_shrank, bool new_string,
+                                     double fraction) {
+    const double f = fraction > 0.0 ? std::min(fraction, 1.0) : 0.0;  // NaN and negatives: 0
+    return {part_rows > 0 && snap_rows >= part_rows && !ids_shrank && !new_string, f};
+}
+
 // ------------------------------------------------------------------ small helpers
 
 // Every distinct value when the column has at most this many (l_discount 11, l_quantity 50);

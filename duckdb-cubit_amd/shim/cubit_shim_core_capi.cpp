@@ -150,6 +150,21 @@ void csc_local_deletes(const uint8_t *present, uint64_t n_present, uint64_t rows
     }
 }
 
+// The update-sync decision; max_changed[i] (n_parts entries, written only when in place) = what
+// partition i of part_rows[i] rows passes to cubit_table_sync_column. Returns 1 = in place.
+int csc_plan_update_sync(uint64_t gpu_rows, uint64_t snap_rows, int ids_shrank, int new_string, double fraction,
+                         const uint64_t *part_rows, uint64_t n_parts, uint64_t *max_changed) {
+    const UpdateSyncPlan plan = PlanUpdateSync(gpu_rows, snap_rows, ids_shrank != 0, new_string != 0, fraction);
+    for (uint64_t i = 0; plan.in_place && i < n_parts; i++) {
+        max_changed[i] = plan.MaxChanged(part_rows[i]);
+    }
+    return plan.in_place;
+}
+
+double csc_default_sync_fraction() {
+    return kDefaultSyncChangedFraction;
+}
+
 int csc_few_distinct(const int64_t *v, const uint64_t *valid, uint64_t n) {
     return FewDistinct(std::vector<int64_t>(v, v + n), std::vector<uint64_t>(valid, valid + (n + 63) / 64));
 }

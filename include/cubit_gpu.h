@@ -552,6 +552,29 @@ int cubit_table_append(cubit_table *t, uint64_t n_new, const int *cols, const vo
  * start_time >= horizon may be served afterwards (as the reference folds versions only below
  * the lowest active start). Records at or past horizon stay. *n_merged = rows merged. */
 int cubit_table_merge_updates(cubit_table *t, int col, uint64_t horizon, uint64_t *n_merged);
+/* Bring `col` to new contents given whole — what a host engine holds after committed UPDATEs:
+ * the column's values, with no list of the rows that changed. values = n_rows entries in the
+ * element type the column was registered with (as data[i] of cubit_table_append: 4 bytes for
+ * INT32 / FLOAT columns and dictionary codes, 8 bytes for every other type; FLOAT / DOUBLE as bit
+ * patterns); validity = LSB-first words, NULL = every row valid. Host pointers, or with
+ * on_device = 1 device pointers read in place (nothing is copied). The changed rows are found on
+ * the device in one pass over the old and the new column: a row changed when its NULL-ness
+ * differs, or when it is valid on both sides and the stored value differs (FLOAT / DOUBLE: the bit
+ * pattern, so -0.0 -> +0.0 is a change and the probe returns what the host holds); two NULLs are
+ * equal whatever their slots hold. *n_changed is written whenever the call succeeds. With
+ * *n_changed > max_changed nothing is changed and *applied = 0 (the caller rebuilds the column);
+ * else *applied = 1 and the base values, the validity and the column's RANGE / EQUALITY / BINS
+ * indexes stand exactly as after cubit_table_merge_updates of one record per changed row (SET
+ * NULL and NULL -> value included: a column registered without validity gets one, statistics
+ * widen, an every-distinct-value index gains keys). *n_changed = 0 invalidates nothing: zone maps
+ * and patched leaves stay. Refused (CUBIT_ERR_INVALID): an unregistered column, a column with
+ * update records outstanding (merge or clear them first), a changed code outside the dictionary.
+ * Extra device memory while the call runs: n_rows x element size + the validity words for host
+ * input (none with on_device), one bitvector, and 17 bytes per changed row (25 for FLOAT /
+ * DOUBLE); an allocation failure returns CUBIT_ERR_OOM. On an error before the records are applied
+ * (every refusal, CUBIT_ERR_OOM of the staging) the table is as it was before the call. */
+int cubit_table_sync_column(cubit_table *t, int col, const void *values, const uint64_t *validity,
+                            int on_device, uint64_t max_changed, uint64_t *n_changed, int *applied);
 
 /* The scan: evaluate a predicate tree (prefix nodes) for transaction `txn` (NULL = see
  * every committed row, no MVCC delta applied) and write the qualifying row ids into
