@@ -1373,7 +1373,8 @@ int copy_validity(cubit_table* t, Column& c, const uint64_t* validity, int on_de
 }
 
 int value_stats(cubit_table* t, const void* data, int type, const uint64_t* validity, uint64_t n,
-                std::vector<int64_t>& distinct, bool want_distinct, int64_t& vmin, int64_t& vmax, bool& any);
+                std::vector<int64_t>& distinct, bool want_distinct, int64_t& vmin, int64_t& vmax, bool& any,
+                uint64_t* n_valid = nullptr);
 
 // The INT32 / INT64 column type a type code's values are held as (INT8, INT16, UINT8, UINT16 →
 // INT32; UINT32, UINT64 → INT64), and the code's value size; false for an unknown code.
@@ -1488,7 +1489,8 @@ constexpr size_t kMaxWideDistinct = 1 << 16;
 // distinct valid values through a presence bitmap of vmax - vmin + 1 bits when the span is
 // below 2^32, else by sorting the valid values on the host.
 int value_stats(cubit_table* t, const void* data, int type, const uint64_t* validity, uint64_t n,
-                std::vector<int64_t>& distinct, bool want_distinct, int64_t& vmin, int64_t& vmax, bool& any) {
+                std::vector<int64_t>& distinct, bool want_distinct, int64_t& vmin, int64_t& vmax, bool& any,
+                uint64_t* n_valid) {
     Column c;
     c.type = type;
     c.data = data;
@@ -1501,6 +1503,7 @@ int value_stats(cubit_table* t, const void* data, int type, const uint64_t* vali
     HIP_CHECK(hipMemcpyAsync(h, stats.p, sizeof(h), hipMemcpyDeviceToHost, t->ctx->stream));
     HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
     any = h[2] > 0;
+    if (n_valid) *n_valid = (uint64_t)h[2];
     vmin = h[0];
     vmax = h[1];
     if (!want_distinct) return CUBIT_OK;
@@ -1548,8 +1551,8 @@ int value_stats(cubit_table* t, const void* data, int type, const uint64_t* vali
 }
 
 int column_stats(cubit_table* t, const Column& c, std::vector<int64_t>& distinct, bool want_distinct,
-                 int64_t& vmin, int64_t& vmax, bool& any) {
-    return value_stats(t, c.data, ktype(c), c.validity, t->n_rows, distinct, want_distinct, vmin, vmax, any);
+                 int64_t& vmin, int64_t& vmax, bool& any, uint64_t* n_valid = nullptr) {
+    return value_stats(t, c.data, ktype(c), c.validity, t->n_rows, distinct, want_distinct, vmin, vmax, any, n_valid);
 }
 
 }  // namespace
@@ -2174,6 +2177,119 @@ extern "C" int cubit_table_add_segment_column(cubit_table* t, int col, int type,
     return CUBIT_OK;
 }
 
+namespace {
+
+// The bitvectors of an index whose keys are chosen (ix: encoding, keys ascending and distinct, the
+// column's statistics): K0 over the column, one pass per kMultiKeys bitvectors. Installs the index.
+int build_index_bitvectors(cubit_table* t, int col, const Column& c, Index&& ix) {
+    const int encoding = ix.encoding;
+    const size_t n_bv = encoding == CUBIT_INDEX_BINS ? ix.keys.size() - 1 : ix.keys.size();
+    // one pass of the column per kMultiKeys bitvectors
+    const int cmp = encoding == CUBIT_INDEX_BINS ? kCmpBetween : encoding == CUBIT_INDEX_RANGE ? CUBIT_CMP_LT : CUBIT_CMP_EQ;
+    for (size_t k0 = 0; k0 < n_bv; k0 += kMultiKeys) {
+        MultiKeyArgs mk{};
+        for (size_t k = k0; k < std::min(n_bv, k0 + kMultiKeys); ++k) {
+            auto b = std::make_unique<DevBuf>();
+            if (int rc = alloc_table_bv(t, *b))
+                return fail(rc, "index bitvector allocation failed after %zu of %zu", ix.bvs.size(), n_bv);
+            mk.c[mk.m] = ix.keys[k];
+            mk.c2[mk.m] = encoding == CUBIT_INDEX_BINS ? ix.keys[k + 1] : 0;
+            mk.out[mk.m] = static_cast<uint64_t*>(b->p);
+            ++mk.m;
+            ix.bvs.push_back(static_cast<uint64_t*>(b->p));
+            ix.owned.push_back(std::move(b));
+            ix.bytes += t->cap_words * 8;
+        }
+        HIP_CHECK(launch_compare_bitvectors(c.data, ktype(c), c.validity, t->n_rows, cmp, mk, t->ctx->stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+    drop_patches(t, col);
+    if (encoding == CUBIT_INDEX_BINS) t->bins[col] = std::move(ix);
+    else t->idx[col] = std::move(ix);
+    return CUBIT_OK;
+}
+
+// CUBIT_QUANTILE_PLAIN_ADDS: the histogram passes without the wave-level pre-aggregation
+// (diagnostic; scripts/quantile_timing.py times both forms)
+bool quantile_wave_agg() {
+    static const bool on = std::getenv("CUBIT_QUANTILE_PLAIN_ADDS") == nullptr;
+    return on;
+}
+
+// Equi-depth edges of a column with m > 0 valid rows whose keys span [vmin, vmax]:
+// q[j - 1] = k[(j·m) / n_bins] for j = 1 … n_bins - 1, k the valid rows' keys in ascending order.
+// A radix select for all n_bins - 1 ranks at once over u = key - vmin, most significant bits first
+// (launch_quantile_hist): after each pass the host walks the counters (≤ 128 KiB) once, finds each
+// rank's bucket and its rank inside the bucket, and hands the distinct buckets to the next pass as
+// its active prefixes. Passes: 1 + ⌈(bits - 12) / d⌉, d = ⌊log2(16,384 / active prefixes)⌋ ≥ 4.
+// With timing on, each pass is a timed launch.
+int quantile_keys(cubit_table* t, const Column& c, uint32_t n_bins, int64_t vmin, int64_t vmax, uint64_t m,
+                  std::vector<int64_t>& q) {
+    cubit_ctx* ctx = t->ctx;
+    hipStream_t s = ctx->stream;
+    const uint64_t span = (uint64_t)vmax - (uint64_t)vmin;  // no signed overflow
+    const uint32_t bits = span ? 64 - (uint32_t)__builtin_clzll(span) : 0;
+    const size_t nt = n_bins - 1;
+    std::vector<uint64_t> prefix(nt, 0), rank(nt), active, next, h(kQuantileCounters);
+    for (size_t j = 0; j < nt; ++j) rank[j] = (uint64_t)(j + 1) * m / n_bins;  // m < 2^47, j < 2^10
+    DevBuf d_counts, d_pre;
+    if (hipMalloc(&d_counts.p, kQuantileCounters * 8) != hipSuccess ||
+        hipMalloc(&d_pre.p, (kQuantileMaxActive + 1) * 8) != hipSuccess)
+        return fail(CUBIT_ERR_OOM, "quantile counters allocation failed");
+    uint32_t consumed = 0;
+    do {
+        const bool first = consumed == 0;
+        QuantileHistArgs a{};
+        a.vmin = vmin;
+        a.bits = bits;
+        a.consumed = consumed;
+        a.n_active = first ? 0 : (uint32_t)active.size();
+        a.d = first ? std::min(bits, kQuantileD0) : quantile_pass_bits(a.n_active, bits - consumed);
+        a.prefixes = static_cast<const uint64_t*>(d_pre.p);
+        a.counts = static_cast<uint64_t*>(d_counts.p);
+        const size_t per = (size_t)1 << a.d, blocks = first ? 1 : active.size();
+        if (!first) HIP_CHECK(hipMemcpyAsync(d_pre.p, active.data(), active.size() * 8, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemsetAsync(d_counts.p, 0, blocks * per * 8, s));
+        hipEvent_t e0, e1;
+        if (int rc = timing_events(ctx, e0, e1)) return rc;
+        HIP_CHECK(launch_quantile_hist(c.data, ktype(c), c.validity, t->n_rows, a, ctx->n_cus, s, e0, e1,
+                                       quantile_wave_agg()));
+        HIP_CHECK(hipMemcpyAsync(h.data(), d_counts.p, blocks * per * 8, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (first) {  // every valid row falls into one pass-0 counter
+            uint64_t total = 0;
+            for (size_t b = 0; b < per; ++b) total += h[b];
+            if (total != m)
+                return fail(CUBIT_ERR_DEVICE, "quantile pass 0 counted %llu rows, the column has %llu valid",
+                            (unsigned long long)total, (unsigned long long)m);
+        }
+        // ranks ascend, so the targets under one prefix are consecutive and their buckets ascend
+        next.clear();
+        size_t j = 0;
+        for (size_t i = 0; i < blocks; ++i) {
+            const uint64_t* cnt = h.data() + i * per;
+            uint64_t below = 0;  // rows of this prefix in the buckets before b
+            size_t b = 0;
+            for (; j < nt && (first || prefix[j] == active[i]); ++j) {
+                while (b < per && below + cnt[b] <= rank[j]) below += cnt[b++];
+                if (b == per)
+                    return fail(CUBIT_ERR_DEVICE, "quantile pass at bit %u: a rank lies past the counted rows", consumed);
+                prefix[j] = (prefix[j] << a.d) | b;
+                rank[j] -= below;  // now its rank among the rows of bucket b
+                if (next.empty() || next.back() != prefix[j]) next.push_back(prefix[j]);
+            }
+        }
+        if (j != nt) return fail(CUBIT_ERR_DEVICE, "quantile pass at bit %u: a prefix went missing", consumed);
+        active.swap(next);
+        consumed += a.d;
+    } while (consumed < bits);
+    q.resize(nt);
+    for (size_t j = 0; j < nt; ++j) q[j] = (int64_t)((uint64_t)vmin + prefix[j]);
+    return CUBIT_OK;
+}
+
+}  // namespace
+
 extern "C" int cubit_table_build_index(cubit_table* t, int col, int encoding, const int64_t* values, uint32_t n) {
     if (!t) return fail(CUBIT_ERR_INVALID, "null table");
     CUBIT_LOCK(t->ctx);
@@ -2237,29 +2353,54 @@ extern "C" int cubit_table_build_index(cubit_table* t, int col, int encoding, co
         ix.keys.erase(std::unique(ix.keys.begin(), ix.keys.end()), ix.keys.end());
         if (encoding == CUBIT_INDEX_BINS && ix.keys.size() < 2) return fail(CUBIT_ERR_INVALID, "bins need >= 2 edges");
     }
-    const size_t n_bv = encoding == CUBIT_INDEX_BINS ? ix.keys.size() - 1 : ix.keys.size();
-    // one pass of the column per kMultiKeys bitvectors
-    const int cmp = encoding == CUBIT_INDEX_BINS ? kCmpBetween : encoding == CUBIT_INDEX_RANGE ? CUBIT_CMP_LT : CUBIT_CMP_EQ;
-    for (size_t k0 = 0; k0 < n_bv; k0 += kMultiKeys) {
-        MultiKeyArgs mk{};
-        for (size_t k = k0; k < std::min(n_bv, k0 + kMultiKeys); ++k) {
-            auto b = std::make_unique<DevBuf>();
-            if (int rc = alloc_table_bv(t, *b))
-                return fail(rc, "index bitvector allocation failed after %zu of %zu", ix.bvs.size(), n_bv);
-            mk.c[mk.m] = ix.keys[k];
-            mk.c2[mk.m] = encoding == CUBIT_INDEX_BINS ? ix.keys[k + 1] : 0;
-            mk.out[mk.m] = static_cast<uint64_t*>(b->p);
-            ++mk.m;
-            ix.bvs.push_back(static_cast<uint64_t*>(b->p));
-            ix.owned.push_back(std::move(b));
-            ix.bytes += t->cap_words * 8;
-        }
-        HIP_CHECK(launch_compare_bitvectors(c.data, ktype(c), c.validity, t->n_rows, cmp, mk, t->ctx->stream));
+    return build_index_bitvectors(t, col, c, std::move(ix));
+}
+
+extern "C" int cubit_table_build_index_quantiles(cubit_table* t, int col, int encoding, uint32_t n_bins, int64_t* keys,
+                                                 uint32_t cap, uint32_t* n_keys) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    auto it = t->cols.find(col);
+    if (it == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column %d not registered", col);
+    if (encoding != CUBIT_INDEX_RANGE && encoding != CUBIT_INDEX_BINS)
+        return fail(CUBIT_ERR_INVALID, "quantile edges serve a RANGE or BINS index, not encoding %d", encoding);
+    if (n_bins < 2 || n_bins > kQuantileMaxActive + 1) return fail(CUBIT_ERR_INVALID, "%u bins (2 … 1,024)", n_bins);
+    if (cap && !keys) return fail(CUBIT_ERR_INVALID, "keys is null");
+    if (int rc = set_device(t->ctx)) return rc;
+    const Column& c = it->second;
+    Index ix;
+    ix.encoding = encoding;
+    std::vector<int64_t> distinct, q;
+    bool any = false;
+    uint64_t m = 0;
+    if (t->n_rows) {
+        if (int rc = column_stats(t, c, distinct, false, ix.vmin, ix.vmax, any, &m)) return rc;
+        if (any)
+            if (int rc = quantile_keys(t, c, n_bins, ix.vmin, ix.vmax, m, q)) return rc;
     }
-    HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
-    drop_patches(t, col);
-    if (encoding == CUBIT_INDEX_BINS) t->bins[col] = std::move(ix);
-    else t->idx[col] = std::move(ix);
+    ix.empty = !any;
+    if (encoding == CUBIT_INDEX_RANGE) {
+        // L(min) is empty: the edges above the minimum. One distinct value or no valid row: no
+        // bitvector, and that is every distinct value, as the n = 0 form of cubit_table_build_index
+        for (int64_t k : q)
+            if (k > ix.vmin && (ix.keys.empty() || k != ix.keys.back())) ix.keys.push_back(k);
+        ix.exact_all = !any || ix.vmin == ix.vmax;
+    } else {
+        if (!any) return fail(CUBIT_ERR_INVALID, "bins need a valid row");
+        // the edge above the maximum, as a key the column's type can carry back: none past INT64_MAX,
+        // and a FLOAT / DOUBLE's next pattern is taken through its key (past +inf: the NaN key; the
+        // NaN key stays, as INT64_MAX does)
+        const int64_t top = ix.vmax == INT64_MAX ? ix.vmax : value_key(c.type, cubit_fp_value(c.type, ix.vmax + 1));
+        ix.keys.push_back(ix.vmin);
+        for (int64_t k : q)
+            if (k != ix.keys.back()) ix.keys.push_back(k);
+        if (top != ix.keys.back()) ix.keys.push_back(top);
+        if (ix.keys.size() < 2) return fail(CUBIT_ERR_INVALID, "bins need >= 2 edges: the column holds one value that nothing follows");
+    }
+    const std::vector<int64_t> chosen = ix.keys;
+    if (int rc = build_index_bitvectors(t, col, c, std::move(ix))) return rc;
+    if (n_keys) *n_keys = (uint32_t)chosen.size();
+    for (size_t k = 0; k < chosen.size() && k < cap; ++k) keys[k] = cubit_fp_value(c.type, chosen[k]);
     return CUBIT_OK;
 }
 

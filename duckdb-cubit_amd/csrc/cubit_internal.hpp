@@ -204,6 +204,39 @@ hipError_t launch_column_minmax(const void* col, int type, const uint64_t* valid
                                 hipStream_t stream);
 hipError_t launch_presence(const void* col, int type, const uint64_t* validity, uint64_t n_rows, int64_t vmin,
                            uint64_t range, uint64_t* bits, hipStream_t stream);
+// Quantile edges (index build): one pass of a multi-target radix select over the normalised key
+// u = (uint64)(key - vmin), which has `bits` significant bits. Pass 0 (consumed = 0) counts the top
+// d bits of u over every valid row into counts[0 … 2^d). A later pass is given the active prefixes
+// (n_active distinct values of u >> (bits - consumed), ascending, on the device) and counts the
+// next d bits of the rows under prefix i into counts[i·2^d … (i + 1)·2^d); every other row is
+// ignored. The counters are 64-bit, zeroed by the caller. A workgroup counts in LDS (32-bit
+// counters, kQuantileCounters of them, beside the prefix table) and adds its non-zero counters to
+// `counts` once at its end, so the caller picks d with n_active · 2^d ≤ kQuantileCounters
+// (quantile_pass_bits); pass 0 counts kQuantileD0 bits (fewer when u has fewer).
+constexpr uint32_t kQuantileCounters = 16384;  // 64 KiB of LDS
+constexpr uint32_t kQuantileD0 = 12;
+constexpr uint32_t kQuantileMaxActive = 1023;  // n_bins ≤ 1,024
+struct QuantileHistArgs {
+    int64_t vmin;
+    uint32_t bits;      // 0 … 64
+    uint32_t consumed;  // bits the earlier passes resolved: 0, or ≥ kQuantileD0
+    uint32_t d;         // bits this pass counts: consumed + d ≤ bits (pass 0 of a single-valued column: 0)
+    uint32_t n_active;  // pass > 0: 1 … kQuantileMaxActive
+    const uint64_t* prefixes;
+    uint64_t* counts;
+};
+// the bits a pass after the first counts: the most that keep every active prefix's counters in LDS
+inline uint32_t quantile_pass_bits(uint32_t n_active, uint32_t bits_left) {
+    uint32_t d = 0;
+    while (d < bits_left && ((uint64_t)n_active << (d + 1)) <= kQuantileCounters) ++d;
+    return d;
+}
+// grid: four (pass 0) or two workgroups per CU, grid-strided. ev0 / ev1 (optional) are stamped by the dispatch, as
+// for launch_eval_decode. wave_agg: a wave whose rows share one counter adds once (the kept form;
+// false is the plain form scripts/quantile_timing.py times it against).
+hipError_t launch_quantile_hist(const void* col, int type, const uint64_t* validity, uint64_t n_rows,
+                                const QuantileHistArgs& a, int n_cus, hipStream_t stream, hipEvent_t ev0 = nullptr,
+                                hipEvent_t ev1 = nullptr, bool wave_agg = true);
 // K5: DuckDB BITPACKING groups → plain values. One record per 2,048-value metadata group
 // (mode: 2 CONSTANT, 3 CONSTANT_DELTA, 4 DELTA_FOR, 5 FOR — BitpackingMode).
 // The host reads each group's header (the T-sized fields before the packed words) into the

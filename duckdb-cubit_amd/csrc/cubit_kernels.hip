@@ -2955,6 +2955,142 @@ __global__ __launch_bounds__(256) void column_zone_stats_kernel(const T* __restr
     }
 }
 
+// ------------------------------------------------------------------ index build: quantile edges
+
+// One pass of the multi-target radix select that picks a column's equi-depth edges
+// (QuantileHistArgs, cubit_internal.hpp). Each thread reads 16 bytes (4 INT32 or 2 INT64 rows) per
+// load, kQuantileUnroll loads in flight, nontemporal like K0's column loads (streamed once); a
+// workgroup owns 512 × kQuantileUnroll such vectors per step and strides by the grid. The validity
+// word is read once per vector (a vector never crosses a 64-row word); NULL rows and rows past
+// n_rows are never counted. Counters are the workgroup's own, in LDS: PASS0 the top d bits of u;
+// otherwise the next d bits under the row's active prefix, found through s_top (for each value of
+// u's top kQuantileTopBits bits, the first active prefix that starts with it: the rows of no
+// active prefix leave after one LDS read) and a binary search among the prefixes that share those
+// bits (one, unless the targets crowd into a narrow range). A row whose counter would fall outside
+// the table is dropped, so a column that changed under the build shows as a wrong total on the
+// host, never as a stray LDS write. WAGG: a wave whose rows of one step (64 lanes × kQuantileUnroll
+// vectors) all fall into one counter adds their number from one lane (a single-valued or sorted
+// column otherwise serialises 64 LDS adds per instruction; measured). At the end
+// every non-zero counter is added to the global 64-bit counters with one atomic, 2^d · n_active ≤
+// 16,384 per workgroup, instead of one global atomic per row.
+constexpr int kQuantileThreads = 512;
+constexpr int kQuantileUnroll = 4;
+constexpr uint32_t kQuantileTopBits = 11;
+static_assert(kQuantileTopBits < kQuantileD0, "every later pass has at least kQuantileTopBits resolved bits");
+static_assert((1u << kQuantileD0) <= kQuantileCounters, "pass 0 fits the counters");
+constexpr uint32_t kQuantileNone = 0xffffffffu;
+
+template <typename T, int FK, bool PASS0, bool WAGG>
+__global__ __launch_bounds__(kQuantileThreads, 4) void quantile_hist_kernel(const T* __restrict__ col,
+                                                                            const uint64_t* __restrict__ validity,
+                                                                            uint64_t n_rows, bool aligned,
+                                                                            QuantileHistArgs a) {
+    constexpr int R = 16 / sizeof(T);  // rows per 16-byte vector
+    constexpr uint32_t RMASK = (1u << R) - 1;
+    __shared__ uint32_t s_cnt[PASS0 ? (1u << kQuantileD0) : kQuantileCounters];
+    __shared__ uint64_t s_pre[PASS0 ? 1 : kQuantileMaxActive];
+    __shared__ uint16_t s_top[PASS0 ? 1 : (1u << kQuantileTopBits) + 1];
+    const uint32_t t = threadIdx.x;
+    const uint32_t n_cnt = PASS0 ? 1u << a.d : a.n_active << a.d;
+    const uint32_t left = a.bits - a.consumed;  // bits of u not resolved before this pass
+    for (uint32_t i = t; i < n_cnt; i += kQuantileThreads) s_cnt[i] = 0;
+    if (!PASS0) {
+        for (uint32_t i = t; i < a.n_active; i += kQuantileThreads) s_pre[i] = a.prefixes[i];
+        __syncthreads();
+        const uint32_t psh = a.consumed - kQuantileTopBits;  // prefix → its top bits
+        for (uint32_t b = t; b <= (1u << kQuantileTopBits); b += kQuantileThreads) {
+            uint32_t lo = 0, hi = a.n_active;  // the first prefix whose top bits are >= b
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if ((uint32_t)(s_pre[mid] >> psh) < b) lo = mid + 1;
+                else hi = mid;
+            }
+            s_top[b] = (uint16_t)lo;
+        }
+    }
+    __syncthreads();
+
+    // the counter of a valid row's value, or kQuantileNone
+    auto bucket = [&](T raw) -> uint32_t {
+        const uint64_t u = (uint64_t)(int64_t)key_of<FK>(raw) - (uint64_t)a.vmin;
+        if (PASS0) {
+            const uint64_t b = u >> (left - a.d);
+            return b < n_cnt ? (uint32_t)b : kQuantileNone;
+        }
+        const uint64_t top = u >> (a.bits - kQuantileTopBits);
+        if (top >= (1u << kQuantileTopBits)) return kQuantileNone;  // u past 2^bits
+        uint32_t lo = s_top[top], hi = s_top[top + 1];
+        if (lo == hi) return kQuantileNone;
+        const uint64_t p = u >> left;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (s_pre[mid] <= p) lo = mid;
+            else hi = mid;
+        }
+        if (s_pre[lo] != p) return kQuantileNone;
+        return (lo << a.d) | ((uint32_t)(u >> (left - a.d)) & ((1u << a.d) - 1));
+    };
+    const uint64_t tile_rows = (uint64_t)kQuantileThreads * kQuantileUnroll * R;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * tile_rows; r0 < n_rows; r0 += (uint64_t)gridDim.x * tile_rows) {
+        T v[kQuantileUnroll][R];
+        uint32_t ok[kQuantileUnroll];
+        if (aligned && r0 + tile_rows <= n_rows) {
+#pragma unroll
+            for (int k = 0; k < kQuantileUnroll; ++k) {
+                const uint64_t row = r0 + ((uint64_t)k * kQuantileThreads + t) * R;
+                if constexpr (sizeof(T) == 4) {
+                    const bp_u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const bp_u32x4*>(col + row));
+                    v[k][0] = (T)q.x, v[k][1] = (T)q.y, v[k][2] = (T)q.z, v[k][3] = (T)q.w;
+                } else {
+                    const u64x2 q = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(col + row));
+                    v[k][0] = (T)q.x, v[k][1] = (T)q.y;
+                }
+                ok[k] = validity ? (uint32_t)(validity[row >> 6] >> (row & 63)) & RMASK : RMASK;
+            }
+        } else {  // the last tile, or a column that does not start on 16 bytes
+#pragma unroll
+            for (int k = 0; k < kQuantileUnroll; ++k) {
+                const uint64_t row = r0 + ((uint64_t)k * kQuantileThreads + t) * R;
+                ok[k] = 0;
+#pragma unroll
+                for (int j = 0; j < R; ++j) {
+                    const bool in = row + j < n_rows;
+                    v[k][j] = in ? __builtin_nontemporal_load(col + row + j) : (T)0;
+                    ok[k] |= in ? 1u << j : 0u;
+                }
+                if (validity && ok[k]) ok[k] &= (uint32_t)(validity[row >> 6] >> (row & 63));
+            }
+        }
+        uint32_t b[kQuantileUnroll][R];
+#pragma unroll
+        for (int k = 0; k < kQuantileUnroll; ++k)
+#pragma unroll
+            for (int j = 0; j < R; ++j) b[k][j] = (ok[k] >> j) & 1u ? bucket(v[k][j]) : kQuantileNone;
+        if (WAGG) {  // one test per step: every row of the wave in one counter (whole waves get here)
+            bool same = true;
+#pragma unroll
+            for (int k = 0; k < kQuantileUnroll; ++k)
+#pragma unroll
+                for (int j = 0; j < R; ++j) same = same && b[k][j] == b[0][0];
+            const uint32_t b0 = __builtin_amdgcn_readfirstlane(b[0][0]);
+            if (__ballot(same && b[0][0] == b0) == ~0ull) {
+                if (b0 != kQuantileNone && (t & 63) == 0) atomicAdd(&s_cnt[b0], 64u * kQuantileUnroll * R);
+                continue;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kQuantileUnroll; ++k)
+#pragma unroll
+            for (int j = 0; j < R; ++j)
+                if (b[k][j] != kQuantileNone) atomicAdd(&s_cnt[b[k][j]], 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < n_cnt; i += kQuantileThreads) {
+        const uint32_t c = s_cnt[i];
+        if (c) atomicAdd(reinterpret_cast<unsigned long long*>(a.counts) + i, (unsigned long long)c);
+    }
+}
+
 // ------------------------------------------------------------------ K4: MVCC
 
 __global__ __launch_bounds__(256) void fill_valid_kernel(uint64_t* __restrict__ words, uint64_t n_rows,
@@ -3574,6 +3710,46 @@ hipError_t launch_presence(const void* col, int type, const uint64_t* validity, 
         else CUBIT_PRESENCE(int64_t, false, 0);
     }
 #undef CUBIT_PRESENCE
+    return hipGetLastError();
+}
+
+hipError_t launch_quantile_hist(const void* col, int type, const uint64_t* validity, uint64_t n_rows,
+                                const QuantileHistArgs& a, int n_cus, hipStream_t stream, hipEvent_t ev0,
+                                hipEvent_t ev1, bool wave_agg) {
+    const bool pass0 = a.consumed == 0;
+    if (a.bits > 64 || !a.counts || (uint64_t)a.consumed + a.d > a.bits) return hipErrorInvalidValue;
+    if (pass0 ? a.d != std::min(a.bits, kQuantileD0)
+              : a.consumed < kQuantileD0 || a.d == 0 || !a.prefixes || a.n_active == 0 ||
+                    a.n_active > kQuantileMaxActive || ((uint64_t)a.n_active << a.d) > kQuantileCounters)
+        return hipErrorInvalidValue;
+    if (n_rows == 0) return hipSuccess;
+    const bool is32 = type_is32(type);
+    const uint64_t tile_rows = (uint64_t)kQuantileThreads * kQuantileUnroll * (is32 ? 4 : 2);
+    const uint64_t tiles = (n_rows + tile_rows - 1) / tile_rows;
+    // two workgroups per CU (the LDS of a later pass allows no more; four in pass 0); more only where
+    // a workgroup's share would reach the 2^32 rows a 32-bit LDS counter holds
+    const uint64_t per_cu = pass0 ? 4 : 2;
+    const uint64_t blocks =
+        std::max<uint64_t>(std::min<uint64_t>(tiles, per_cu * (uint64_t)std::max(n_cus, 1)), (n_rows >> 31) + 1);
+    const dim3 grid((unsigned)blocks), block(kQuantileThreads);
+    const bool aligned = reinterpret_cast<uintptr_t>(col) % 16 == 0;
+#define CUBIT_QHIST_W(T, FK, P0, W)                                                                              \
+    hipExtLaunchKernelGGL((quantile_hist_kernel<T, FK, P0, W>), grid, block, 0, stream, ev0, ev1, 0,             \
+                          static_cast<const T*>(col), validity, n_rows, aligned, a)
+#define CUBIT_QHIST(T, FK)                                 \
+    do {                                                   \
+        if (pass0 && wave_agg) CUBIT_QHIST_W(T, FK, true, true);    \
+        else if (pass0) CUBIT_QHIST_W(T, FK, true, false);          \
+        else if (wave_agg) CUBIT_QHIST_W(T, FK, false, true);       \
+        else CUBIT_QHIST_W(T, FK, false, false);                    \
+    } while (0)
+    // FLOAT / DOUBLE columns come as their key columns (key_type), as to the compare kernels
+    if (type_is_fp(type)) return hipErrorInvalidValue;
+    if (type == kTypeUInt64) CUBIT_QHIST(int64_t, 3);
+    else if (is32) CUBIT_QHIST(int32_t, 0);
+    else CUBIT_QHIST(int64_t, 0);
+#undef CUBIT_QHIST
+#undef CUBIT_QHIST_W
     return hipGetLastError();
 }
 

@@ -384,6 +384,16 @@ class CubitTable:
         else:
             L.check(self.lib.cubit_table_build_index(self.handle, col, encoding, None, 0))
 
+    def build_index_quantiles(self, col: int, n_bins: int, encoding: int = L.INDEX_RANGE) -> np.ndarray:
+        """Build a RANGE (or BINS) index whose edges are the column's equi-depth quantiles, chosen on
+        the GPU. Returns the keys as int64, in the form cubit_table_build_index takes them: FLOAT /
+        DOUBLE bit patterns, the bits of UBIGINT values (view as uint64), dictionary codes for VARCHAR."""
+        keys = np.empty(n_bins + 1, dtype=np.int64)
+        n = C.c_uint32()
+        L.check(self.lib.cubit_table_build_index_quantiles(self.handle, col, encoding, n_bins, keys.ctypes.data,
+                                                           len(keys), C.byref(n)))
+        return keys[: n.value].copy()
+
     def save_index(self, col: int, encoding: int, path) -> None:
         L.check(self.lib.cubit_table_save_index(self.handle, col, encoding, str(path).encode()))
 

@@ -78,12 +78,14 @@ namespace duckdb {
 // ------------------------------------------------------------------ registry
 
 // A bitmap index the attach builds on one column (cubit_table_build_index): its encoding and
-// keys (empty = every distinct value of the column).
+// keys (empty = every distinct value of the column), or the number of equi-depth bins whose edges
+// each partition chooses from its rows (cubit_table_build_index_quantiles).
 struct CubitIndexSpec {
     column_t column;
     int encoding;  // CUBIT_INDEX_RANGE / _EQUALITY / _BINS
     vector<int64_t> keys;
     vector<string> str_keys;  // a VARCHAR column's keys (sorted, distinct)
+    uint32_t quantile_bins = 0;  // `column=encoding~count`: no keys, count bins
 };
 
 // One GPU partition per attached table: the device context, the cubit_table, which storage
@@ -1373,7 +1375,11 @@ static std::shared_ptr<CubitPartitionSet> BuildPartition(CubitAttached &attached
             }
             bool named = false;
             for (auto &ix : attached.indexes) {
-                if (ix.column == col) {
+                if (ix.column == col && ix.quantile_bins) {
+                    Check(cubit_table_build_index_quantiles(t, (int)col, ix.encoding, ix.quantile_bins, nullptr, 0,
+                                                            nullptr));
+                    named = true;
+                } else if (ix.column == col) {
                     vector<cubit_string> strs;  // a dictionary column's keys as cubit_strings
                     vector<int64_t> addrs;
                     strs.reserve(ix.str_keys.size());
@@ -1645,6 +1651,7 @@ static vector<CubitIndexSpec> ParseIndexSpec(DuckTableEntry &entry, const string
         CubitIndexSpec ix;
         ix.column = def.StorageOid();
         ix.encoding = item.encoding;
+        ix.quantile_bins = item.quantile_bins;
         const auto phys = def.GetType().InternalType();
         if (Traits(phys).dict) {
             for (auto &lit : item.literals) {
@@ -1659,13 +1666,16 @@ static vector<CubitIndexSpec> ParseIndexSpec(DuckTableEntry &entry, const string
             }
             core::SortKeys(Traits(phys).upload_type, ix.keys);
         }
-        if (!core::EnoughKeys(ix.encoding, ix.keys.size() + ix.str_keys.size())) {
+        if (!ix.quantile_bins && !core::EnoughKeys(ix.encoding, ix.keys.size() + ix.str_keys.size())) {
             throw InvalidInputException("cubit_attach: bins on %s need at least two edges", item.name);
         }
         out.push_back(std::move(ix));
     }
     if (status == core::SpecStatus::MissingEquals) {
         throw InvalidInputException("cubit_attach: index item '%s' is not column=encoding[:values]", bad);
+    }
+    if (status == core::SpecStatus::BadCount) {
+        throw InvalidInputException("cubit_attach: bin count '%s' is not a number in 2 … 1,024 on its own", bad);
     }
     if (status == core::SpecStatus::UnknownEncoding) {
         throw InvalidInputException("cubit_attach: unknown index encoding '%s'", bad);

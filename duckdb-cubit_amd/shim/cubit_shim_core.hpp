@@ -392,17 +392,35 @@ inline void PackStrings(const std::vector<std::string> &strs, std::vector<char> 
 
 // ------------------------------------------------------------------ index specification
 
-// Index specification of cubit_attach's third argument: `column=encoding[:v1,v2,…]` items
-// separated by ';' — encoding range | equality | bins, values as SQL literals of the column's
-// type (dates, decimals), e.g.
+// Index specification of cubit_attach's third argument: `column=encoding[:v1,v2,…]` or
+// `column=encoding~count` items separated by ';' — encoding range | equality | bins, values as SQL
+// literals of the column's type (dates, decimals); `~count` (range and bins only, 2 … 1,024, no
+// literal list beside it) asks for that many equi-depth bins, their edges chosen from the column's
+// quantiles (cubit_table_build_index_quantiles), e.g.
 //   'l_shipdate=range:1994-01-01,1995-01-01;l_shipdate=bins:1992-01-01,1993-01-01,…;l_discount=range'
+//   'l_shipdate=range~64;l_extendedprice=bins~256'
 struct IndexItem {
     std::string name;  // the column, not yet resolved
     int encoding;      // CUBIT_INDEX_RANGE / _EQUALITY / _BINS
     std::vector<std::string> literals;  // not yet cast; empty = every distinct value
+    uint32_t quantile_bins = 0;  // `~count`: the equi-depth bins to choose edges for (0 = none asked)
 };
 
-enum class SpecStatus { Ok, MissingEquals, UnknownEncoding };
+enum class SpecStatus { Ok, MissingEquals, UnknownEncoding, BadCount };
+
+static constexpr uint32_t kMinQuantileBins = 2, kMaxQuantileBins = 1024;
+
+// `count` as a decimal number in kMinQuantileBins … kMaxQuantileBins (digits only), or 0
+inline uint32_t ParseQuantileBins(const std::string &count) {
+    uint32_t v = 0;
+    for (char c : count) {
+        if (c < '0' || c > '9' || v > kMaxQuantileBins) {
+            return 0;
+        }
+        v = v * 10 + (uint32_t)(c - '0');
+    }
+    return !count.empty() && v >= kMinQuantileBins && v <= kMaxQuantileBins ? v : 0;
+}
 
 // Split on a delimiter as reading a stream up to each delimiter does: no item after a final
 // delimiter, none for an empty text.
@@ -432,8 +450,9 @@ inline void TrimText(std::string &s) {
 
 // The items of `spec` in order (empty items skipped, whitespace around items, names, encodings and
 // literals dropped, encodings in any letter case). At the first malformed item the split stops:
-// `items` holds the ones before it, `bad` the offending text — the item without a '=', or the
-// encoding that is none of the three.
+// `items` holds the ones before it, `bad` the offending text — the item without a '=', the
+// encoding that is none of the three (`equality~8` among them: an equality index takes no count),
+// or the count as written, with what follows it (`1025`, `x`, `8:1,2`).
 inline SpecStatus SplitIndexSpec(const std::string &spec, std::vector<IndexItem> &items, std::string &bad) {
     items.clear();
     for (auto item : SplitText(spec, ';')) {
@@ -454,6 +473,24 @@ inline SpecStatus SplitIndexSpec(const std::string &spec, std::vector<IndexItem>
         std::string enc = rest.substr(0, colon);
         for (auto &c : enc) {
             c = c >= 'A' && c <= 'Z' ? (char)(c - 'A' + 'a') : c;
+        }
+        // a '~' before any ':' (one inside a literal belongs to the literal) opens the bin count
+        const auto tilde = enc.find('~');
+        if (tilde != std::string::npos) {
+            std::string count = enc.substr(tilde + 1);
+            enc = enc.substr(0, tilde);
+            TrimText(enc);
+            TrimText(count);
+            if (enc != "range" && enc != "bins") {
+                bad = enc + "~" + count;
+                return SpecStatus::UnknownEncoding;
+            }
+            ix.quantile_bins = ParseQuantileBins(count);
+            if (ix.quantile_bins == 0 || colon != std::string::npos) {
+                bad = rest.substr(rest.find('~') + 1);
+                TrimText(bad);
+                return SpecStatus::BadCount;
+            }
         }
         TrimText(enc);
         if (enc == "range") {

@@ -204,6 +204,23 @@ int csc_split_index_spec(const char *spec, char *items, uint64_t cap, char *bad,
     return (int)st;
 }
 
+// The same split with each item's bin count (`~count`, 0 where none): counts[i] for i < min(cap, *n),
+// *n = the items split. Returns the SpecStatus (… 3 bad count); bad as above.
+int csc_split_index_spec_counts(const char *spec, uint32_t *counts, uint64_t cap, uint64_t *n, char *bad,
+                                uint64_t bad_cap) {
+    std::vector<IndexItem> parsed;
+    std::string offending;
+    const SpecStatus st = SplitIndexSpec(spec, parsed, offending);
+    *n = parsed.size();
+    for (size_t i = 0; i < parsed.size() && i < cap; i++) {
+        counts[i] = parsed[i].quantile_bins;
+    }
+    if (PutText(offending, bad, bad_cap)) {
+        return -1;
+    }
+    return (int)st;
+}
+
 // sorted and deduplicated in place; returns how many remain
 uint64_t csc_sort_keys(int upload_type, int64_t *keys, uint64_t n) {
     std::vector<int64_t> k(keys, keys + n);

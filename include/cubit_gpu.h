@@ -488,6 +488,32 @@ int cubit_table_last_k0_order(cubit_table *t, int32_t *cols, uint32_t cap, uint3
  * distinct values of the column" (exact for every constant). RANGE / EQUALITY replace the
  * column's primary index; BINS (n >= 2 edges) adds a secondary binned index. */
 int cubit_table_build_index(cubit_table *t, int col, int encoding, const int64_t *values, uint32_t n);
+/* Build a RANGE or BINS index on `col` whose edges are the column's equi-depth quantiles, chosen
+ * on the GPU by a radix select over the column where it lies (a few streaming histogram passes; the
+ * column is not copied to the host): for columns with too many distinct values for the n = 0 form
+ * above (dates, prices, TIMESTAMPs, ids, DOUBLE measures). With k the comparison keys of the m valid
+ * rows in ascending order and q_j = k[(j * m) / n_bins] (integer division), j = 1 ... n_bins - 1:
+ *   CUBIT_INDEX_RANGE: the keys are the distinct q_j above k[0] (L(min) is empty). A column with one
+ *     distinct value, or with no valid row, gets an index with no bitvector, as with n = 0 above.
+ *   CUBIT_INDEX_BINS: the edges are the distinct values of {k[0]} + {q_j} + {k[m-1] + 1}; where
+ *     k[m-1] + 1 is not a key (k[m-1] is INT64_MAX, UINT64_MAX or a FLOAT / DOUBLE NaN), k[m-1]
+ *     itself (one past a FLOAT / DOUBLE +inf is the NaN key). Fewer than two edges, or m = 0:
+ *     CUBIT_ERR_INVALID.
+ *   CUBIT_INDEX_EQUALITY (quantile keys are not the values an equality index wants), n_bins outside
+ *   2 ... 1,024 and an unregistered column: CUBIT_ERR_INVALID.
+ * Each bin then holds about the same share of the rows, so a constant that is not a key costs the
+ * same candidate check wherever it falls. The result is an ordinary index with explicit keys: it is
+ * saved, loaded, appended to, merged into and synced like one from cubit_table_build_index.
+ * keys / cap / n_keys (each optional, as cubit_table_last_k0_order's): *n_keys = the number of keys
+ * chosen, keys[i] for i < min(cap, *n_keys) the keys in the form cubit_table_build_index takes them:
+ * bit patterns for FLOAT / DOUBLE (cubit_fp_value of the key), the bits of UINT64 values. For a
+ * dictionary column (VARCHAR) they are codes, where cubit_table_build_index takes addresses of
+ * cubit_strings.
+ * Memory: up to n_bins bitvectors of n_rows / 8 bytes each (64 bins over 600 M rows: 4.8 GB). Each
+ * partition of a multi-device table chooses its own edges from its own rows. With timing on, each
+ * histogram pass is a timed launch. */
+int cubit_table_build_index_quantiles(cubit_table *t, int col, int encoding, uint32_t n_bins, int64_t *keys,
+                                      uint32_t cap, uint32_t *n_keys);
 /* Number of bitvectors and bytes held by the indexes on col, all encodings (0 if none). */
 int cubit_table_index_info(cubit_table *t, int col, uint32_t *n_bitvectors, uint64_t *bytes);
 /* Index persistence (the reference persists index state through IndexStorageInfo,
