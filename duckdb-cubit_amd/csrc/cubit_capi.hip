@@ -1376,31 +1376,22 @@ int value_stats(cubit_table* t, const void* data, int type, const uint64_t* vali
                 std::vector<int64_t>& distinct, bool want_distinct, int64_t& vmin, int64_t& vmax, bool& any,
                 uint64_t* n_valid = nullptr);
 
-// The INT32 / INT64 column type a type code's values are held as (INT8, INT16, UINT8, UINT16 →
-// INT32; UINT32, UINT64 → INT64), and the code's value size; false for an unknown code.
-bool storage_of(int type, int& col_type, uint64_t& src_size) {
-    switch (type) {
-    case CUBIT_TYPE_INT32: col_type = CUBIT_TYPE_INT32, src_size = 4; return true;
-    case CUBIT_TYPE_INT64: col_type = CUBIT_TYPE_INT64, src_size = 8; return true;
-    case CUBIT_TYPE_INT8: case CUBIT_TYPE_UINT8: col_type = CUBIT_TYPE_INT32, src_size = 1; return true;
-    case CUBIT_TYPE_INT16: case CUBIT_TYPE_UINT16: col_type = CUBIT_TYPE_INT32, src_size = 2; return true;
-    case CUBIT_TYPE_UINT32: col_type = CUBIT_TYPE_INT64, src_size = 4; return true;
-    case CUBIT_TYPE_UINT64: col_type = CUBIT_TYPE_UINT64, src_size = 8; return true;  // the bits, keyed
-    case CUBIT_TYPE_FLOAT: col_type = CUBIT_TYPE_FLOAT, src_size = 4; return true;
-    case CUBIT_TYPE_DOUBLE: col_type = CUBIT_TYPE_DOUBLE, src_size = 8; return true;
-    case CUBIT_TYPE_VARCHAR: col_type = CUBIT_TYPE_VARCHAR, src_size = 4; return true;  // codes
-    default: return false;
-    }
+// Store a column under `col`; what depended on the old one goes: its patched leaves and the zone
+// maps (drop_patches), its indexes.
+int install_column(cubit_table* t, int col, Column&& c) {
+    t->cols[col] = std::move(c);
+    drop_patches(t, col);
+    t->idx.erase(col);
+    t->bins.erase(col);
+    return CUBIT_OK;
 }
 
 // A column of a narrower or unsigned type code: its values (host or device) widened on the
 // device into an owned INT32 / INT64 column (UINT64 columns are held as their bits, keyed).
 int widen_column(cubit_table* t, Column& c, int type, const void* data, const uint64_t* validity, int on_device) {
-    int col_type = 0;
-    uint64_t ssz = 0;
-    storage_of(type, col_type, ssz);
-    const uint64_t esz = col_type == CUBIT_TYPE_INT32 ? 4 : 8;
-    c.type = col_type;
+    const TypeInfo& ti = *type_info(type);
+    const uint64_t ssz = ti.size, esz = ti.col_type == CUBIT_TYPE_INT32 ? 4 : 8;
+    c.type = ti.col_type;
     if (t->n_rows == 0) return CUBIT_OK;
     hipStream_t s = t->ctx->stream;
     DevBuf staged;
@@ -1613,20 +1604,14 @@ extern "C" int cubit_table_add_column(cubit_table* t, int col, int type, const v
                                       int on_device) {
     if (!t || !data) return fail(CUBIT_ERR_INVALID, "null argument");
     CUBIT_LOCK(t->ctx);
-    int col_type = 0;
-    uint64_t src_size = 0;
-    if (!storage_of(type, col_type, src_size)) return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
+    if (!type_info(type)) return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
     if (type == CUBIT_TYPE_VARCHAR)
         return fail(CUBIT_ERR_INVALID, "a VARCHAR column is registered with its dictionary (cubit_table_add_dict_column)");
     if (col < 0) return fail(CUBIT_ERR_INVALID, "column %d", col);
     if (int rc = set_device(t->ctx)) return rc;
     Column c;
     if (int rc = copy_column(t, c, type, data, validity, on_device)) return rc;
-    t->cols[col] = std::move(c);
-    drop_patches(t, col);
-    t->idx.erase(col);
-    t->bins.erase(col);
-    return CUBIT_OK;
+    return install_column(t, col, std::move(c));
 }
 
 // ------------------------------------------------------------------ VARCHAR dictionaries
@@ -1761,11 +1746,7 @@ extern "C" int cubit_table_add_dict_column(cubit_table* t, int col, cubit_dict* 
             return fail(CUBIT_ERR_INVALID, "code %lld outside the dictionary's %llu strings",
                         (long long)(vmin < 0 ? vmin : vmax), (unsigned long long)c.dict->size());
     }
-    t->cols[col] = std::move(c);
-    drop_patches(t, col);
-    t->idx.erase(col);
-    t->bins.erase(col);
-    return CUBIT_OK;
+    return install_column(t, col, std::move(c));
 }
 
 namespace {
@@ -1780,401 +1761,226 @@ int check_codes(const Column& c, const int64_t* v, const uint8_t* valid, uint64_
 }
 }  // namespace
 
-// The segments' T (a CUBIT_TYPE_* code): its byte size and signedness, the column type its
-// values widen to and the BpGroup::tnorm that carries T's arithmetic there.
-struct SegType {
-    uint32_t tsz;
-    bool sgn;
-    int col_type;
-    uint8_t tnorm;
-};
-bool seg_type_of(int type, SegType& st) {
-    switch (type) {
-    case CUBIT_TYPE_INT32: st = {4, true, CUBIT_TYPE_INT32, 0}; return true;
-    case CUBIT_TYPE_INT64: st = {8, true, CUBIT_TYPE_INT64, 0}; return true;
-    case CUBIT_TYPE_INT8: st = {1, true, CUBIT_TYPE_INT32, 8 | 0x80}; return true;
-    case CUBIT_TYPE_INT16: st = {2, true, CUBIT_TYPE_INT32, 16 | 0x80}; return true;
-    case CUBIT_TYPE_UINT8: st = {1, false, CUBIT_TYPE_INT32, 8}; return true;
-    case CUBIT_TYPE_UINT16: st = {2, false, CUBIT_TYPE_INT32, 16}; return true;
-    case CUBIT_TYPE_UINT32: st = {4, false, CUBIT_TYPE_INT64, 32}; return true;
-    case CUBIT_TYPE_UINT64: st = {8, false, CUBIT_TYPE_UINT64, 0}; return true;
-    default: return false;
+// ------------------------------------------------------------------ columns given as DuckDB segments
+// The three entry points below share one path: a plan of what the segments ask of the device
+// (SegmentPlan, cubit_segments.hpp: walked and bounds-checked on the host), one build that uploads
+// it and launches a stage for each part the plan has, and install_column. A call refused at any
+// point leaves the table as it was.
+
+namespace {
+
+// The plan of a column's segments: segment i has codec seg_codecs[i], or `codec` for all when
+// seg_codecs is null. With seg_codecs every segment adds its runs to the one run list: a CONSTANT
+// segment one run of its value, an RLE segment its runs, the others a placeholder run that their
+// stage writes over. Ends with the segments' rows checked against the partition's.
+int plan_segments(const cubit_table* t, const TypeInfo& ti, const uint8_t* bytes, uint64_t n_bytes,
+                  const uint64_t* seg_offsets, const uint64_t* seg_rows, const int32_t* seg_codecs, int codec,
+                  const int64_t* seg_constants, uint32_t n_segments, SegmentPlan& p) {
+    const uint64_t bytes_padded = (n_bytes + 15) / 16 * 16;
+    char err[192];
+    for (uint32_t sg = 0; sg < n_segments; ++sg) {
+        const uint64_t rows = seg_rows[sg], row = p.rows;
+        if (seg_codecs) codec = seg_codecs[sg];
+        if (codec != CUBIT_CODEC_CONSTANT && (!bytes || seg_offsets[sg] > n_bytes))
+            return fail(CUBIT_ERR_INVALID, "segment %u: bad offset", sg);
+        int64_t run = 0;  // the placeholder
+        switch (codec) {
+        case CUBIT_CODEC_CONSTANT:
+            if (!seg_constants) return fail(CUBIT_ERR_INVALID, "segment %u: CONSTANT without a value", sg);
+            run = seg_constants[sg];
+            p.rows += rows;
+            break;
+        case CUBIT_CODEC_RLE:
+            if (int rc = walk_rle_segment(bytes, n_bytes, seg_offsets[sg], rows, ti, sg, p, err, sizeof(err)))
+                return fail(rc, "%s", err);
+            continue;  // its own runs
+        case CUBIT_CODEC_BITPACKING:
+            if (int rc = walk_bp_segment(bytes, n_bytes, seg_offsets[sg], rows, ti, bytes_padded, sg, p, err, sizeof(err)))
+                return fail(rc, "%s", err);
+            break;
+        case CUBIT_CODEC_UNCOMPRESSED:
+            if (seg_offsets[sg] % ti.size || rows * ti.size > n_bytes - seg_offsets[sg])
+                return fail(CUBIT_ERR_INVALID, "segment %u: %llu values past the bytes", sg, (unsigned long long)rows);
+            p.plain.push_back({seg_offsets[sg], rows, row});
+            p.rows += rows;
+            break;
+        default:
+            return fail(CUBIT_ERR_UNSUPPORTED, "segment %u: codec %d", sg, codec);
+        }
+        if (seg_codecs) {
+            p.vals.push_back(run);
+            p.ends.push_back(row + rows);
+        }
     }
+    if (p.rows != t->n_rows)
+        return fail(CUBIT_ERR_INVALID, "segments hold %llu rows, partition has %llu", (unsigned long long)p.rows,
+                    (unsigned long long)t->n_rows);
+    return CUBIT_OK;
 }
 
-// The groups of one BITPACKING segment (at byte `base`, `rows` rows from partition row `row`):
-// each group's mode, header fields and packed words, bounds-checked; packed runs off the 4-byte
-// alignment are copied behind the bytes (`moved`, at bytes_padded + …).
-int parse_bp_segment(const uint8_t* bytes, uint64_t n_bytes, uint64_t base, uint64_t rows, uint64_t row,
-                     const SegType& st, uint64_t bytes_padded, std::vector<BpGroup>& groups,
-                     std::vector<uint8_t>& moved, uint32_t sg) {
-    const uint64_t tsz = st.tsz;
-    if (base % 8 || base + 8 > n_bytes) return fail(CUBIT_ERR_INVALID, "segment %u: bad offset", sg);
-    uint64_t meta_end;
-    std::memcpy(&meta_end, bytes + base, 8);
-    const uint64_t n_groups = (rows + 2047) / 2048;
-    if (meta_end > n_bytes - base || meta_end < 8 + 4 * n_groups)
-        return fail(CUBIT_ERR_INVALID, "segment %u: bad metadata offset", sg);
-    for (uint64_t g = 0; g < n_groups; ++g) {
-        uint32_t enc;
-        std::memcpy(&enc, bytes + base + meta_end - 4 * (g + 1), 4);
-        BpGroup bg{};
-        const uint32_t mode = enc >> 24;
-        const uint64_t data_off = base + (enc & 0x00ffffffu);
-        bg.mode = (uint8_t)mode;
-        bg.tnorm = st.tnorm;
-        bg.row_start = row + g * 2048;
-        bg.count = (uint32_t)std::min<uint64_t>(2048, rows - g * 2048);
-        // header fields (BitpackingScanState::LoadNextGroup, bitpacking.cpp:620-690)
-        const uint64_t n_fields = mode == 2 ? 1 : (mode == 3 || mode == 5) ? 2 : mode == 4 ? 3 : 0;
-        if (n_fields == 0)
-            return fail(CUBIT_ERR_INVALID, "segment %u group %llu: mode %u", sg, (unsigned long long)g, mode);
-        if (data_off < base + 8 || data_off + n_fields * tsz > n_bytes)
-            return fail(CUBIT_ERR_INVALID, "segment %u group %llu: out of bounds", sg, (unsigned long long)g);
-        auto field = [&](uint64_t i) {
-            uint64_t v = 0;  // T's bits, zero-extended (the kernels work mod 2^bits: bp_norm)
-            std::memcpy(&v, bytes + data_off + i * tsz, tsz);
-            return v;
-        };
-        bg.base = field(0);
-        uint64_t packed = 0;
-        if (mode == 3) {
-            bg.aux = field(1);
-        } else if (mode == 4 || mode == 5) {
-            const uint64_t w = field(1) & 0xff;  // the reference reads the width as a T, uses its low byte
-            if (w > 8 * tsz) return fail(CUBIT_ERR_INVALID, "segment %u group %llu: width %u", sg, (unsigned long long)g, (unsigned)w);
-            bg.width = (uint16_t)w;
-            if (mode == 4) bg.aux = field(2);
-            packed = ((uint64_t)bg.count + 31) / 32 * 32 * w / 8;
+// The column of a plan, built in stream order, each stage only when the plan has something for it:
+// rle_expand_kernel writes the runs, bitunpack_kernel (K5) unpacks the BITPACKING groups over their
+// rows, the UNCOMPRESSED spans are copied (INT32, INT64, UINT64: the values as held) or widened over
+// theirs. With timing on, the start event goes to the first kernel and the stop event to the last,
+// or behind the last span. `type` is the segments' T, `bytes` the caller's segment bytes (read only
+// by the groups and spans), `what` names the entry point in an allocation failure.
+// keep_packed: the column keeps the bytes, the group records and the group of each 2,048-row
+// vector's first row (SumArgs::a_vgroup) for the packed filter and the packed fused sum.
+int build_segment_column(cubit_table* t, int type, const TypeInfo& ti, const SegmentPlan& p, const uint8_t* bytes,
+                         uint64_t n_bytes, const uint64_t* validity, bool keep_packed, const char* what, Column& c) {
+    if (int rc = set_device(t->ctx)) return rc;
+    hipStream_t s = t->ctx->stream;
+    const bool wide = ti.col_type != CUBIT_TYPE_INT32;
+    const uint64_t esz = wide ? 8 : 4;
+    const uint64_t bytes_padded = (n_bytes + 15) / 16 * 16;
+    const bool has_runs = !p.ends.empty(), has_groups = !p.groups.empty(), has_plain = !p.plain.empty();
+    std::vector<int32_t> narrow;
+    if (!wide) narrow.assign(p.vals.begin(), p.vals.end());
+    const uint64_t n_tiles = (t->n_rows + 2047) / 2048;
+    std::vector<uint32_t> vgroup;
+    if (keep_packed) {
+        vgroup.assign(std::max<uint64_t>(n_tiles, 1), 0);
+        for (uint64_t v = 0, g = 0; v < n_tiles; ++v) {
+            while (g + 1 < p.groups.size() && p.groups[g].row_start + p.groups[g].count <= v * 2048) ++g;
+            vgroup[v] = (uint32_t)g;
         }
-        bg.words_off = data_off + n_fields * tsz;
-        if (bg.words_off + packed > n_bytes)
-            return fail(CUBIT_ERR_INVALID, "segment %u group %llu: out of bounds", sg, (unsigned long long)g);
-        if (packed && bg.words_off % 4) {
-            const uint64_t at = moved.size();
-            moved.resize(at + (packed + 15) / 16 * 16, 0);
-            std::memcpy(moved.data() + at, bytes + bg.words_off, packed);
-            bg.words_off = bytes_padded + at;
+    }
+    DevBuf d_vals, d_ends, d_tiles;
+    auto out = std::make_unique<DevBuf>(), d_bytes = std::make_unique<DevBuf>(), d_groups = std::make_unique<DevBuf>(),
+         d_vgroup = std::make_unique<DevBuf>();
+    // bytes + 16: the kernels stage packed words with 16-byte-aligned loads that may run past the end
+    if (hipMalloc(&out->p, std::max<uint64_t>(t->n_rows * esz, 16)) != hipSuccess ||
+        (has_runs && (hipMalloc(&d_vals.p, std::max<uint64_t>(p.vals.size() * esz, 16)) != hipSuccess ||
+                      hipMalloc(&d_ends.p, std::max<uint64_t>(p.ends.size() * 8, 16)) != hipSuccess ||
+                      hipMalloc(&d_tiles.p, (n_tiles + 1) * 8) != hipSuccess)) ||
+        ((has_groups || has_plain) && hipMalloc(&d_bytes->p, bytes_padded + p.moved.size() + 16) != hipSuccess) ||
+        (has_groups && hipMalloc(&d_groups->p, p.groups.size() * sizeof(BpGroup)) != hipSuccess) ||
+        (keep_packed && hipMalloc(&d_vgroup->p, vgroup.size() * 4) != hipSuccess))
+        return fail(CUBIT_ERR_OOM, "%s column allocation failed", what);
+    if (has_runs) {
+        HIP_CHECK(hipMemcpyAsync(d_vals.p, wide ? (const void*)p.vals.data() : (const void*)narrow.data(),
+                                 p.vals.size() * esz, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_ends.p, p.ends.data(), p.ends.size() * 8, hipMemcpyHostToDevice, s));
+    }
+    if (has_groups || has_plain) {
+        HIP_CHECK(hipMemcpyAsync(d_bytes->p, bytes, n_bytes, hipMemcpyHostToDevice, s));
+        if (!p.moved.empty())
+            HIP_CHECK(hipMemcpyAsync(static_cast<uint8_t*>(d_bytes->p) + bytes_padded, p.moved.data(), p.moved.size(),
+                                     hipMemcpyHostToDevice, s));
+    }
+    if (has_groups)
+        HIP_CHECK(hipMemcpyAsync(d_groups->p, p.groups.data(), p.groups.size() * sizeof(BpGroup), hipMemcpyHostToDevice, s));
+    if (keep_packed) HIP_CHECK(hipMemcpyAsync(d_vgroup->p, vgroup.data(), vgroup.size() * 4, hipMemcpyHostToDevice, s));
+    hipEvent_t e0, e1;
+    if (int rc = timing_events(t->ctx, e0, e1)) return rc;
+    if (has_runs)
+        HIP_CHECK(launch_rle_expand(d_vals.p, static_cast<const uint64_t*>(d_ends.p), p.ends.size(), t->n_rows, wide ? 1 : 0,
+                                    static_cast<uint64_t*>(d_tiles.p), out->p, s, e0, has_groups || has_plain ? nullptr : e1));
+    if (has_groups)
+        HIP_CHECK(launch_bitunpack(static_cast<const uint8_t*>(d_bytes->p), static_cast<const BpGroup*>(d_groups->p),
+                                   p.groups.size(), ti.col_type, out->p, s, has_runs ? nullptr : e0, has_plain ? nullptr : e1));
+    for (const SegmentPlan::Span& pl : p.plain) {
+        const uint8_t* src = static_cast<const uint8_t*>(d_bytes->p) + pl.off;
+        uint8_t* dst = static_cast<uint8_t*>(out->p) + pl.row * esz;
+        if (ti.size == esz)
+            HIP_CHECK(hipMemcpyAsync(dst, src, pl.rows * esz, hipMemcpyDeviceToDevice, s));
+        else
+            HIP_CHECK(launch_widen(src, type, pl.rows, dst, s));
+    }
+    if (e1 && has_plain) HIP_CHECK(hipEventRecord(e1, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    c.type = ti.col_type;
+    c.data = out->p;
+    c.cap_rows = t->n_rows;
+    c.owned.push_back(std::move(out));
+    if (keep_packed) {
+        c.bp_bytes = std::move(d_bytes);
+        c.bp_groups = std::move(d_groups);
+        c.bp_vgroup = std::move(d_vgroup);
+        c.bp_n_groups = p.groups.size();
+        c.bp_simple_width = 0;
+        if (std::all_of(p.groups.begin(), p.groups.end(), [](const BpGroup& g) {
+                return g.mode == 2 || g.mode == 3 || (g.mode == 5 && g.width <= 32);
+            })) {
+            int wmax = 1;
+            for (const BpGroup& g : p.groups)
+                if (g.mode == 5) wmax = std::max<int>(wmax, g.width);
+            c.bp_simple_width = wmax;
         }
-        groups.push_back(bg);
+    }
+    if (validity) {
+        if (int rc = copy_validity(t, c, validity, 0)) return rc;
+        HIP_CHECK(hipStreamSynchronize(s));
     }
     return CUBIT_OK;
 }
 
-// DuckDB BITPACKING segments → device column (K5). The host walks each segment's metadata
-// (header = end of the metadata words, one word per 2,048-row group, highest address first:
-// BitpackingScanState / LoadNextGroup, bitpacking.cpp:620-690), checks every group's bounds,
-// and the GPU unpacks all groups in parallel. A T of 1 or 2 bytes leaves its groups' packed
-// runs off the 4-byte alignment the kernels' word loads need (the header fields are T-sized,
-// WriteData, :448-451): those runs are copied behind the segment bytes, 16-aligned.
+}  // namespace
+
+// DuckDB BITPACKING segments → device column: bitunpack_kernel alone, and the column keeps the
+// packed form.
 extern "C" int cubit_table_add_bitpacked_column(cubit_table* t, int col, int type, const uint8_t* bytes,
                                                 uint64_t n_bytes, const uint64_t* seg_offsets,
                                                 const uint64_t* seg_rows, uint32_t n_segments,
                                                 const uint64_t* validity) {
     if (!t) return fail(CUBIT_ERR_INVALID, "null argument");
     CUBIT_LOCK(t->ctx);
-    SegType st;
-    if (!seg_type_of(type, st)) return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
+    const TypeInfo* ti = segment_type(type);
+    if (!ti) return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
     if (col < 0) return fail(CUBIT_ERR_INVALID, "column %d", col);
+    Column c;
     if (t->n_rows == 0 && n_segments == 0) {  // empty partition, no segments
-        Column c;
-        c.type = st.col_type;
-        t->cols[col] = std::move(c);
-        drop_patches(t, col);
-        t->idx.erase(col);
-        t->bins.erase(col);
-        return CUBIT_OK;
+        c.type = ti->col_type;
+        return install_column(t, col, std::move(c));
     }
     if (!bytes || !seg_offsets || !seg_rows || n_segments == 0) return fail(CUBIT_ERR_INVALID, "null argument");
-    if (int rc = set_device(t->ctx)) return rc;
-    const uint64_t esz = st.col_type == CUBIT_TYPE_INT32 ? 4 : 8;
-    const uint64_t bytes_padded = (n_bytes + 15) / 16 * 16;
-    std::vector<BpGroup> groups;
-    std::vector<uint8_t> moved;  // packed runs copied to 16-aligned offsets behind the bytes
-    uint64_t row = 0;
-    for (uint32_t sg = 0; sg < n_segments; ++sg) {
-        if (int rc = parse_bp_segment(bytes, n_bytes, seg_offsets[sg], seg_rows[sg], row, st, bytes_padded, groups,
-                                      moved, sg))
-            return rc;
-        row += seg_rows[sg];
-    }
-    if (row != t->n_rows)
-        return fail(CUBIT_ERR_INVALID, "segments hold %llu rows, partition has %llu", (unsigned long long)row,
-                    (unsigned long long)t->n_rows);
-    // the probe's random access (SumArgs::a_vgroup): the group of each vector's first row
-    const uint64_t n_vec = (t->n_rows + 2047) / 2048;
-    std::vector<uint32_t> vgroup(std::max<uint64_t>(n_vec, 1), 0);
-    for (uint64_t v = 0, g = 0; v < n_vec; ++v) {
-        while (g + 1 < groups.size() && groups[g].row_start + groups[g].count <= v * 2048) ++g;
-        vgroup[v] = (uint32_t)g;
-    }
-    hipStream_t s = t->ctx->stream;
-    DevBuf d_bytes, d_groups, d_vgroup;
-    auto out = std::make_unique<DevBuf>();
-    // +16: the kernels stage packed words with 16-byte-aligned loads that may run past the end
-    if (hipMalloc(&d_bytes.p, bytes_padded + moved.size() + 16) != hipSuccess ||
-        hipMalloc(&d_groups.p, groups.size() * sizeof(BpGroup)) != hipSuccess ||
-        hipMalloc(&out->p, std::max<uint64_t>(t->n_rows * esz, 16)) != hipSuccess ||
-        hipMalloc(&d_vgroup.p, vgroup.size() * 4) != hipSuccess)
-        return fail(CUBIT_ERR_OOM, "bitpacked column allocation failed");
-    HIP_CHECK(hipMemcpyAsync(d_bytes.p, bytes, n_bytes, hipMemcpyHostToDevice, s));
-    if (!moved.empty())
-        HIP_CHECK(hipMemcpyAsync(static_cast<uint8_t*>(d_bytes.p) + bytes_padded, moved.data(), moved.size(),
-                                 hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_vgroup.p, vgroup.data(), vgroup.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_groups.p, groups.data(), groups.size() * sizeof(BpGroup), hipMemcpyHostToDevice, s));
-    hipEvent_t e0, e1;
-    if (int rc = timing_events(t->ctx, e0, e1)) return rc;
-    HIP_CHECK(launch_bitunpack(static_cast<const uint8_t*>(d_bytes.p), static_cast<const BpGroup*>(d_groups.p),
-                               groups.size(), st.col_type, out->p, s, e0, e1));
-    HIP_CHECK(hipStreamSynchronize(s));
-    Column c;
-    c.type = st.col_type;
-    c.data = out->p;
-    c.cap_rows = t->n_rows;
-    c.owned.push_back(std::move(out));
-    c.bp_bytes = std::make_unique<DevBuf>();
-    c.bp_groups = std::make_unique<DevBuf>();
-    std::swap(c.bp_bytes->p, d_bytes.p);
-    std::swap(c.bp_groups->p, d_groups.p);
-    c.bp_vgroup = std::make_unique<DevBuf>();
-    std::swap(c.bp_vgroup->p, d_vgroup.p);
-    c.bp_n_groups = groups.size();
-    c.bp_simple_width = 0;
-    if (std::all_of(groups.begin(), groups.end(), [](const BpGroup& g) {
-            return g.mode == 2 || g.mode == 3 || (g.mode == 5 && g.width <= 32);
-        })) {
-        int wmax = 1;
-        for (const BpGroup& g : groups)
-            if (g.mode == 5) wmax = std::max<int>(wmax, g.width);
-        c.bp_simple_width = wmax;
-    }
-    if (validity) {
-        if (int rc = copy_validity(t, c, validity, 0)) return rc;
-        HIP_CHECK(hipStreamSynchronize(s));
-    }
-    t->cols[col] = std::move(c);
-    drop_patches(t, col);
-    t->idx.erase(col);
-    t->bins.erase(col);
-    return CUBIT_OK;
+    SegmentPlan p;
+    if (int rc = plan_segments(t, *ti, bytes, n_bytes, seg_offsets, seg_rows, nullptr, CUBIT_CODEC_BITPACKING, nullptr,
+                               n_segments, p))
+        return rc;
+    if (int rc = build_segment_column(t, type, *ti, p, bytes, n_bytes, validity, true, "bitpacked", c)) return rc;
+    return install_column(t, col, std::move(c));
 }
 
-// The runs of one RLE segment (at byte `base`, `rows` rows from partition row `row`): values as
-// T widened to int64 (T's sign), each run's end row appended to `ends`.
-int parse_rle_segment(const uint8_t* bytes, uint64_t n_bytes, uint64_t base, uint64_t rows, uint64_t row,
-                      const SegType& st, std::vector<int64_t>& vals, std::vector<uint64_t>& ends, uint32_t sg) {
-    const uint64_t tsz = st.tsz;
-    if (base + 8 > n_bytes) return fail(CUBIT_ERR_INVALID, "segment %u: bad offset", sg);
-    uint64_t off;
-    std::memcpy(&off, bytes + base, 8);
-    if (off < 8 || off > n_bytes - base) return fail(CUBIT_ERR_INVALID, "segment %u: bad run-length offset", sg);
-    uint64_t covered = 0;
-    for (uint64_t k = 0; covered < rows; ++k) {
-        if (8 + (k + 1) * tsz > off || off + 2 * (k + 1) > n_bytes - base)
-            return fail(CUBIT_ERR_INVALID, "segment %u: runs cover %llu of %llu rows", sg, (unsigned long long)covered,
-                        (unsigned long long)rows);
-        uint16_t len;
-        std::memcpy(&len, bytes + base + off + 2 * k, 2);
-        uint64_t raw = 0;  // T's bits, zero-extended, then widened as T
-        std::memcpy(&raw, bytes + base + 8 + k * tsz, tsz);
-        int64_t v = (int64_t)raw;
-        if (st.sgn && tsz < 8) v = (int64_t)(raw << (64 - 8 * tsz)) >> (64 - 8 * tsz);
-        covered += len;
-        if (covered > rows) return fail(CUBIT_ERR_INVALID, "segment %u: runs overrun its rows", sg);
-        vals.push_back(v);
-        ends.push_back(row + covered);
-    }
-    return CUBIT_OK;
-}
-
-// DuckDB RLE segments → device column. Each segment (rle.cpp RLECompressState::FlushSegment,
-// :190-205: 8-byte header = offset of the uint16 run lengths, the run values as T from byte 8,
-// the lengths after them) is walked on the host: run lengths are read until they cover the
-// segment's rows (RLEScanState, :248-277 — zero-length runs, which a run of exactly 65,535 rows
-// leaves behind, included), each value widened to the column's type as the BITPACKING path does.
-// Only the runs cross to the device, and rle_expand_kernel writes the column.
+// DuckDB RLE segments → device column: only the runs cross to the device, rle_expand_kernel writes
+// the column.
 extern "C" int cubit_table_add_rle_column(cubit_table* t, int col, int type, const uint8_t* bytes, uint64_t n_bytes,
                                           const uint64_t* seg_offsets, const uint64_t* seg_rows, uint32_t n_segments,
                                           const uint64_t* validity) {
     if (!t) return fail(CUBIT_ERR_INVALID, "null argument");
     CUBIT_LOCK(t->ctx);
-    SegType st;
-    if (!seg_type_of(type, st)) return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
+    const TypeInfo* ti = segment_type(type);
+    if (!ti) return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
     if (col < 0) return fail(CUBIT_ERR_INVALID, "column %d", col);
     if (n_segments && (!bytes || !seg_offsets || !seg_rows)) return fail(CUBIT_ERR_INVALID, "null argument");
-    const bool wide = st.col_type != CUBIT_TYPE_INT32;
-    std::vector<int64_t> vals;
-    std::vector<uint64_t> ends;
-    uint64_t row = 0;
-    for (uint32_t sg = 0; sg < n_segments; ++sg) {
-        if (int rc = parse_rle_segment(bytes, n_bytes, seg_offsets[sg], seg_rows[sg], row, st, vals, ends, sg)) return rc;
-        row += seg_rows[sg];
-    }
-    if (row != t->n_rows)
-        return fail(CUBIT_ERR_INVALID, "segments hold %llu rows, partition has %llu", (unsigned long long)row,
-                    (unsigned long long)t->n_rows);
-    if (int rc = set_device(t->ctx)) return rc;
-    hipStream_t s = t->ctx->stream;
-    const uint64_t esz = wide ? 8 : 4;
-    std::vector<int32_t> narrow;
-    if (!wide) narrow.assign(vals.begin(), vals.end());
-    DevBuf d_vals, d_ends, d_tiles;
-    auto out = std::make_unique<DevBuf>();
-    const uint64_t n_tiles = (t->n_rows + 2047) / 2048;
-    if (hipMalloc(&d_vals.p, std::max<uint64_t>(vals.size() * esz, 16)) != hipSuccess ||
-        hipMalloc(&d_ends.p, std::max<uint64_t>(ends.size() * 8, 16)) != hipSuccess ||
-        hipMalloc(&d_tiles.p, (n_tiles + 1) * 8) != hipSuccess ||
-        hipMalloc(&out->p, std::max<uint64_t>(t->n_rows * esz, 16)) != hipSuccess)
-        return fail(CUBIT_ERR_OOM, "RLE column allocation failed");
-    if (!vals.empty()) {
-        HIP_CHECK(hipMemcpyAsync(d_vals.p, wide ? (const void*)vals.data() : (const void*)narrow.data(),
-                                 vals.size() * esz, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(d_ends.p, ends.data(), ends.size() * 8, hipMemcpyHostToDevice, s));
-    }
-    hipEvent_t e0, e1;
-    if (int rc = timing_events(t->ctx, e0, e1)) return rc;
-    HIP_CHECK(launch_rle_expand(d_vals.p, static_cast<const uint64_t*>(d_ends.p), ends.size(), t->n_rows, wide ? 1 : 0,
-                                static_cast<uint64_t*>(d_tiles.p), out->p, s, e0, e1));
-    HIP_CHECK(hipStreamSynchronize(s));
+    SegmentPlan p;
     Column c;
-    c.type = st.col_type;
-    c.data = out->p;
-    c.cap_rows = t->n_rows;
-    c.owned.push_back(std::move(out));
-    if (validity) {
-        if (int rc = copy_validity(t, c, validity, 0)) return rc;
-        HIP_CHECK(hipStreamSynchronize(s));
-    }
-    t->cols[col] = std::move(c);
-    drop_patches(t, col);
-    t->idx.erase(col);
-    t->bins.erase(col);
-    return CUBIT_OK;
+    if (int rc = plan_segments(t, *ti, bytes, n_bytes, seg_offsets, seg_rows, nullptr, CUBIT_CODEC_RLE, nullptr,
+                               n_segments, p))
+        return rc;
+    if (int rc = build_segment_column(t, type, *ti, p, bytes, n_bytes, validity, false, "RLE", c)) return rc;
+    return install_column(t, col, std::move(c));
 }
 
 // A column given as DuckDB segments of mixed codecs, one per row group as DuckDB's checkpoint chose
-// (UNCOMPRESSED, CONSTANT, RLE, BITPACKING). One run list covers every row: CONSTANT segments
-// are one run of their value, RLE segments their runs, the others a placeholder run; the GPU
-// expands it (rle_expand_kernel), then unpacks the BITPACKING groups over their rows
-// (bitunpack_kernel) and copies / widens the UNCOMPRESSED values over theirs, in stream order.
+// (UNCOMPRESSED, CONSTANT, RLE, BITPACKING); bytes may be null when every segment is CONSTANT. The
+// packed form is not kept, even when every segment is BITPACKING.
 extern "C" int cubit_table_add_segment_column(cubit_table* t, int col, int type, const uint8_t* bytes, uint64_t n_bytes,
                                               const uint64_t* seg_offsets, const uint64_t* seg_rows,
                                               const int32_t* seg_codecs, const int64_t* seg_constants,
                                               uint32_t n_segments, const uint64_t* validity) {
     if (!t) return fail(CUBIT_ERR_INVALID, "null argument");
     CUBIT_LOCK(t->ctx);
-    SegType st;
-    if (!seg_type_of(type, st)) return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
+    const TypeInfo* ti = segment_type(type);
+    if (!ti) return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
     if (col < 0) return fail(CUBIT_ERR_INVALID, "column %d", col);
     if (n_segments && (!seg_offsets || !seg_rows || !seg_codecs)) return fail(CUBIT_ERR_INVALID, "null argument");
-    const bool wide = st.col_type != CUBIT_TYPE_INT32;
-    const uint64_t esz = wide ? 8 : 4;
-    const uint64_t bytes_padded = (n_bytes + 15) / 16 * 16;
-    std::vector<int64_t> vals;
-    std::vector<uint64_t> ends;
-    std::vector<BpGroup> groups;
-    std::vector<uint8_t> moved;
-    struct Plain {
-        uint64_t off, rows, row;
-    };
-    std::vector<Plain> plain;
-    uint64_t row = 0;
-    for (uint32_t sg = 0; sg < n_segments; ++sg) {
-        const uint64_t rows = seg_rows[sg];
-        const int codec = seg_codecs[sg];
-        const bool needs_bytes = codec != CUBIT_CODEC_CONSTANT;
-        if (needs_bytes && (!bytes || seg_offsets[sg] > n_bytes)) return fail(CUBIT_ERR_INVALID, "segment %u: bad offset", sg);
-        switch (codec) {
-        case CUBIT_CODEC_CONSTANT:
-            if (!seg_constants) return fail(CUBIT_ERR_INVALID, "segment %u: CONSTANT without a value", sg);
-            vals.push_back(seg_constants[sg]);
-            ends.push_back(row + rows);
-            break;
-        case CUBIT_CODEC_RLE:
-            if (int rc = parse_rle_segment(bytes, n_bytes, seg_offsets[sg], rows, row, st, vals, ends, sg)) return rc;
-            break;
-        case CUBIT_CODEC_BITPACKING:
-            if (int rc = parse_bp_segment(bytes, n_bytes, seg_offsets[sg], rows, row, st, bytes_padded, groups, moved, sg))
-                return rc;
-            vals.push_back(0);  // placeholder, unpacked over below
-            ends.push_back(row + rows);
-            break;
-        case CUBIT_CODEC_UNCOMPRESSED:
-            if (seg_offsets[sg] % st.tsz || rows * st.tsz > n_bytes - seg_offsets[sg])
-                return fail(CUBIT_ERR_INVALID, "segment %u: %llu values past the bytes", sg, (unsigned long long)rows);
-            plain.push_back({seg_offsets[sg], rows, row});
-            vals.push_back(0);  // placeholder, copied over below
-            ends.push_back(row + rows);
-            break;
-        default:
-            return fail(CUBIT_ERR_UNSUPPORTED, "segment %u: codec %d", sg, codec);
-        }
-        row += rows;
-    }
-    if (row != t->n_rows)
-        return fail(CUBIT_ERR_INVALID, "segments hold %llu rows, partition has %llu", (unsigned long long)row,
-                    (unsigned long long)t->n_rows);
-    if (int rc = set_device(t->ctx)) return rc;
-    hipStream_t s = t->ctx->stream;
-    std::vector<int32_t> narrow;
-    if (!wide) narrow.assign(vals.begin(), vals.end());
-    const bool has_bytes = !groups.empty() || !plain.empty();
-    DevBuf d_vals, d_ends, d_tiles, d_bytes, d_groups;
-    auto out = std::make_unique<DevBuf>();
-    const uint64_t n_tiles = (t->n_rows + 2047) / 2048;
-    if (hipMalloc(&d_vals.p, std::max<uint64_t>(vals.size() * esz, 16)) != hipSuccess ||
-        hipMalloc(&d_ends.p, std::max<uint64_t>(ends.size() * 8, 16)) != hipSuccess ||
-        hipMalloc(&d_tiles.p, (n_tiles + 1) * 8) != hipSuccess ||
-        hipMalloc(&out->p, std::max<uint64_t>(t->n_rows * esz, 16)) != hipSuccess ||
-        (has_bytes && hipMalloc(&d_bytes.p, bytes_padded + moved.size() + 16) != hipSuccess) ||
-        (!groups.empty() && hipMalloc(&d_groups.p, groups.size() * sizeof(BpGroup)) != hipSuccess))
-        return fail(CUBIT_ERR_OOM, "segment column allocation failed");
-    if (!vals.empty()) {
-        HIP_CHECK(hipMemcpyAsync(d_vals.p, wide ? (const void*)vals.data() : (const void*)narrow.data(),
-                                 vals.size() * esz, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(d_ends.p, ends.data(), ends.size() * 8, hipMemcpyHostToDevice, s));
-    }
-    if (has_bytes) {
-        HIP_CHECK(hipMemcpyAsync(d_bytes.p, bytes, n_bytes, hipMemcpyHostToDevice, s));
-        if (!moved.empty())
-            HIP_CHECK(hipMemcpyAsync(static_cast<uint8_t*>(d_bytes.p) + bytes_padded, moved.data(), moved.size(),
-                                     hipMemcpyHostToDevice, s));
-    }
-    hipEvent_t e0, e1;
-    if (int rc = timing_events(t->ctx, e0, e1)) return rc;
-    HIP_CHECK(launch_rle_expand(d_vals.p, static_cast<const uint64_t*>(d_ends.p), ends.size(), t->n_rows, wide ? 1 : 0,
-                                static_cast<uint64_t*>(d_tiles.p), out->p, s, e0, groups.empty() && plain.empty() ? e1 : nullptr));
-    if (!groups.empty()) {
-        HIP_CHECK(hipMemcpyAsync(d_groups.p, groups.data(), groups.size() * sizeof(BpGroup), hipMemcpyHostToDevice, s));
-        HIP_CHECK(launch_bitunpack(static_cast<const uint8_t*>(d_bytes.p), static_cast<const BpGroup*>(d_groups.p),
-                                   groups.size(), st.col_type, out->p, s, nullptr, plain.empty() ? e1 : nullptr));
-    }
-    for (size_t i = 0; i < plain.size(); ++i) {
-        const Plain& pl = plain[i];
-        const uint8_t* src = static_cast<const uint8_t*>(d_bytes.p) + pl.off;
-        uint8_t* dst = static_cast<uint8_t*>(out->p) + pl.row * esz;
-        if (st.tsz == esz)  // INT32, INT64, UINT64: the values as held
-            HIP_CHECK(hipMemcpyAsync(dst, src, pl.rows * esz, hipMemcpyDeviceToDevice, s));
-        else
-            HIP_CHECK(launch_widen(src, type, pl.rows, dst, s));
-    }
-    if (e1 && !plain.empty()) HIP_CHECK(hipEventRecord(e1, s));
-    HIP_CHECK(hipStreamSynchronize(s));
+    SegmentPlan p;
     Column c;
-    c.type = st.col_type;
-    c.data = out->p;
-    c.cap_rows = t->n_rows;
-    c.owned.push_back(std::move(out));
-    if (validity) {
-        if (int rc = copy_validity(t, c, validity, 0)) return rc;
-        HIP_CHECK(hipStreamSynchronize(s));
-    }
-    t->cols[col] = std::move(c);
-    drop_patches(t, col);
-    t->idx.erase(col);
-    t->bins.erase(col);
-    return CUBIT_OK;
+    if (int rc = plan_segments(t, *ti, bytes, n_bytes, seg_offsets, seg_rows, seg_codecs, 0, seg_constants, n_segments, p))
+        return rc;
+    if (int rc = build_segment_column(t, type, *ti, p, bytes, n_bytes, validity, false, "segment", c)) return rc;
+    return install_column(t, col, std::move(c));
 }
 
 namespace {

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "cubit_segments.hpp"
+
 namespace cubit {
 
 // DuckDB storage geometry (src/include/duckdb/common/vector_size.hpp:16-20,
@@ -237,24 +239,7 @@ inline uint32_t quantile_pass_bits(uint32_t n_active, uint32_t bits_left) {
 hipError_t launch_quantile_hist(const void* col, int type, const uint64_t* validity, uint64_t n_rows,
                                 const QuantileHistArgs& a, int n_cus, hipStream_t stream, hipEvent_t ev0 = nullptr,
                                 hipEvent_t ev1 = nullptr, bool wave_agg = true);
-// K5: DuckDB BITPACKING groups → plain values. One record per 2,048-value metadata group
-// (mode: 2 CONSTANT, 3 CONSTANT_DELTA, 4 DELTA_FOR, 5 FOR — BitpackingMode).
-// The host reads each group's header (the T-sized fields before the packed words) into the
-// record, so a workgroup's only dependent load chain is record → packed words.
-struct BpGroup {
-    uint64_t words_off;  // byte offset of the packed words (FOR / DELTA_FOR)
-    uint64_t row_start;  // first row of the group
-    uint64_t base;       // CONSTANT value | CONSTANT_DELTA first | FOR minimum | DELTA_FOR min_delta (T bits)
-    uint64_t aux;        // CONSTANT_DELTA delta | DELTA_FOR delta_offset (T bits)
-    uint32_t count;      // rows in the group (≤ 2,048)
-    uint8_t mode;
-    // the segments' T when narrower than the column's values (an 8- / 16-bit T in an INT32
-    // column, UINT32 in an INT64 column): its bits | 0x80 when signed; 0 = T is the column's
-    // type. Decoded values are taken mod 2^bits and sign- or zero-extended (bp_norm), which is
-    // T's own wrap-around arithmetic
-    uint8_t tnorm;
-    uint16_t width;      // bit width of the packed values (FOR / DELTA_FOR)
-};
+// K5: DuckDB BITPACKING groups (BpGroup, cubit_segments.hpp) → plain values
 hipError_t launch_bitunpack(const uint8_t* bytes, const BpGroup* groups, uint64_t n_groups, int type, void* out,
                             hipStream_t stream, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 // strings → codes of a sorted dictionary, all on the device (NULL rows 0; a missing string -1,
