@@ -2294,7 +2294,8 @@ extern "C" int cubit_table_save_index(cubit_table* t, int col, int encoding, con
               (h.n_keys == 0 || std::fwrite(ix->keys.data(), 8, h.n_keys, f) == h.n_keys);
     std::vector<uint64_t> host(ok ? t->nwp : 0);
     for (size_t k = 0; ok && k < ix->bvs.size(); ++k) {
-        if (hipMemcpy(host.data(), ix->bvs[k], t->nwp * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+        if (hipMemcpyAsync(host.data(), ix->bvs[k], t->nwp * 8, hipMemcpyDeviceToHost, t->ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(t->ctx->stream) != hipSuccess) {
             std::fclose(f);
             return fail(CUBIT_ERR_HIP, "index download failed");
         }
@@ -2328,6 +2329,10 @@ extern "C" int cubit_table_load_index(cubit_table* t, int col, const char* path)
             return bad("index was built against another dictionary");
     } else if (lc.dict) {
         return bad("a version-1 index file does not name its dictionary");
+    } else if (lc.type != CUBIT_TYPE_INT32 && lc.type != CUBIT_TYPE_INT64) {
+        // version 1 predates the typed columns: its keys are raw values, where a UBIGINT, FLOAT or
+        // DOUBLE index is keyed by comparison keys
+        return bad("a version-1 index file holds raw-value keys, this column's type needs comparison keys");
     }
     if (h.n_rows != t->n_rows || h.nwp != t->nwp) return bad("index was built for a partition of another size");
     if (h.encoding > CUBIT_INDEX_BINS) return bad("unknown encoding");
@@ -2350,7 +2355,9 @@ extern "C" int cubit_table_load_index(cubit_table* t, int col, const char* path)
             std::fclose(f);
             return fail(CUBIT_ERR_OOM, "index bitvector allocation failed");
         }
-        if (hipMemcpy(b->p, host.data(), t->nwp * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        // on the context stream, behind alloc_table_bv's memset; host is refilled by the next read
+        if (hipMemcpyAsync(b->p, host.data(), t->nwp * 8, hipMemcpyHostToDevice, t->ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(t->ctx->stream) != hipSuccess) {
             std::fclose(f);
             return fail(CUBIT_ERR_HIP, "index upload failed");
         }
@@ -2377,8 +2384,9 @@ extern "C" int cubit_table_set_deletes(cubit_table* t, const int64_t* rows, cons
         hipMalloc(&t->del_ids->p, std::max<uint64_t>(n, 1) * 8) != hipSuccess)
         return fail(CUBIT_ERR_OOM, "delete list allocation failed");
     if (n) {
-        HIP_CHECK(hipMemcpy(t->del_rows->p, rows, n * 8, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(t->del_ids->p, ids, n * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpyAsync(t->del_rows->p, rows, n * 8, hipMemcpyHostToDevice, t->ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(t->del_ids->p, ids, n * 8, hipMemcpyHostToDevice, t->ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(t->ctx->stream));  // rows / ids are the caller's
     }
     t->n_del = n;
     t->del_ids_sorted.assign(ids, ids + n);
@@ -2470,6 +2478,7 @@ int store_updates(cubit_table* t, int col, const int64_t* rows, const int64_t* v
             if (u.valid_at(i)) vv.push_back(value_key(type, u.h_values[i]));
         u.stat_values = distinct_sorted(vv.data(), vv.size());
     }
+    hipStream_t s = t->ctx->stream;
     u.rows = std::make_unique<DevBuf>();
     u.values = std::make_unique<DevBuf>();
     u.versions = std::make_unique<DevBuf>();
@@ -2478,15 +2487,16 @@ int store_updates(cubit_table* t, int col, const int64_t* rows, const int64_t* v
         hipMalloc(&u.versions->p, std::max<uint64_t>(n, 1) * 8) != hipSuccess)
         return fail(CUBIT_ERR_OOM, "update list allocation failed");
     if (n) {
-        HIP_CHECK(hipMemcpy(u.rows->p, u.h_rows.data(), n * 8, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(u.values->p, u.h_values.data(), n * 8, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(u.versions->p, u.h_versions.data(), n * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpyAsync(u.rows->p, u.h_rows.data(), n * 8, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(u.values->p, u.h_values.data(), n * 8, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(u.versions->p, u.h_versions.data(), n * 8, hipMemcpyHostToDevice, s));
     }
     if (u.any_null) {
         u.valids = std::make_unique<DevBuf>();
         if (hipMalloc(&u.valids->p, n) != hipSuccess) return fail(CUBIT_ERR_OOM, "update list allocation failed");
-        HIP_CHECK(hipMemcpy(u.valids->p, u.h_valids.data(), n, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpyAsync(u.valids->p, u.h_valids.data(), n, hipMemcpyHostToDevice, s));
     }
+    HIP_CHECK(hipStreamSynchronize(s));  // uploaded on return, and a failed copy is reported here
     t->upd[col] = std::move(u);
     return CUBIT_OK;
 }

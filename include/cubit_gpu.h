@@ -14,7 +14,10 @@
  * local). Output buffers are caller-owned device buffers. A context owns one HIP stream
  * (cubit_ctx_set_stream), a claim ticket and a tile directory; every call on a context or on
  * its tables holds the context's mutex, so DuckDB's pipeline threads may share it (calls
- * serialise; GPU work stays asynchronous on the stream). Results named "last" belong to the
+ * serialise; GPU work stays asynchronous on the stream). Once cubit_ctx_create has returned, the
+ * library issues every kernel, copy and memset on the context's stream (or on a copy stream made
+ * from it) and nothing on the null stream, so a context bound to a hipStreamNonBlocking stream
+ * orders its work behind whatever the caller has pending there. Results named "last" belong to the
  * context's most recent call: threads that need their own give themselves a context each.
  * Row ids are int64 (DuckDB ROW_TYPE). Bitvectors are LSB-first 64-bit words, the layout
  * of DuckDB's ValidityMask (src/include/duckdb/common/types/validity_mask.hpp:22,164-168).
@@ -523,7 +526,8 @@ int cubit_table_index_info(cubit_table *t, int col, uint32_t *n_bitvectors, uint
  * data: load it only beside the column it was built from. It names the column's type and, for a
  * dictionary column (VARCHAR, HUGEINT / UHUGEINT), its dictionary (a fingerprint of the entries):
  * a load onto a column of another type or against another dictionary is refused
- * (CUBIT_ERR_INVALID). */
+ * (CUBIT_ERR_INVALID). A version-1 file names neither and holds raw values as keys: it loads onto
+ * an INT32 / INT64 column only (UBIGINT, FLOAT and DOUBLE indexes are keyed by comparison keys). */
 int cubit_table_save_index(cubit_table *t, int col, int encoding, const char *path);
 int cubit_table_load_index(cubit_table *t, int col, const char *path);
 

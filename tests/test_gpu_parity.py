@@ -625,6 +625,50 @@ def test_index_save_and_load(ctx, tmp_path):
         t2.load_index(0, junk)
 
 
+def test_version_1_index_file_loads_on_integer_columns_only(ctx, tmp_path):
+    """A version-1 index file (no column type, raw values as keys) is refused on UBIGINT and DOUBLE
+    columns, whose indexes are keyed by comparison keys — it used to load and select the wrong
+    bitvectors; on an INT64 column it loads and scans to the oracle's rows. The version-1 file is a
+    saved version-2 file with version = 1 at byte 8 and the 16-byte tail after the 72-byte header
+    removed."""
+    rng = np.random.default_rng(61)
+    n = 70_001
+    cols = [rng.integers(-50, 50, n).astype(np.int64),
+            rng.integers(2 ** 63 - 25, 2 ** 63 + 25, n, dtype=np.uint64),
+            (rng.integers(-50, 50, n) / 4).astype(np.float64)]
+    t = CubitTable(ctx, n)
+    v1 = []
+    for c, a in enumerate(cols):
+        t.add_column(c, a)
+        t.build_index(c, L.INDEX_RANGE)
+        f = tmp_path / f"v2_{c}.cubitix"
+        t.save_index(c, L.INDEX_RANGE, f)
+        b = bytearray(f.read_bytes())
+        assert b[8:12] == (2).to_bytes(4, "little")
+        b[8:12] = (1).to_bytes(4, "little")
+        v1.append(tmp_path / f"v1_{c}.cubitix")
+        v1[-1].write_bytes(bytes(b[:72] + b[88:]))
+    t2 = CubitTable(ctx, n)
+    for c, a in enumerate(cols):
+        t2.add_column(c, a)
+    for c in (1, 2):
+        with pytest.raises(L.CubitError, match="version-1 index file holds raw-value keys"):
+            t2.load_index(c, v1[c])
+        assert t2.index_info(c) == (0, 0)
+        t2.load_index(c, tmp_path / f"v2_{c}.cubitix")  # the version-2 file of the same index loads
+    t2.load_index(0, v1[0])
+    assert t2.index_info(0) == t.index_info(0)
+    ocols = [O.Column(a) for a in cols]
+    for fs in (F.TableFilterSet({0: F.ConstantFilter("<", -7)}),
+               F.TableFilterSet({0: F.ConjunctionAndFilter([F.ConstantFilter(">=", -20), F.ConstantFilter("<", 31)])}),
+               F.TableFilterSet({0: F.ConstantFilter("=", 12), 1: F.ConstantFilter(">=", 2 ** 63),
+                                 2: F.ConstantFilter("<", 3.25)})):
+        ref = O.table_scan(ocols, F.serialize(fs), n)
+        assert len(ref) > 0 and np.array_equal(t2.scan(fs), ref), fs
+    t.close()
+    t2.close()
+
+
 def test_concurrent_scans_share_a_context(ctx):
     """DuckDB's pipeline threads call the scan concurrently (pipeline.cpp:113-125): scans from
     four threads on one context and table, each with its own output buffers and predicate,
