@@ -1,6 +1,8 @@
 // C ABI of libcubitgpu.so (include/cubit_gpu.h) and the host-side planner that turns a
 // DuckDB-style predicate tree (TableFilter mirror) into bitvector programs for the
-// fused eval/decode kernel.
+// fused eval/decode kernel. The expressions, the emitter that writes a program and the walk of a
+// filter tree are in cubit_program.hpp (HIP-free, run on the CPU by tests/program_core.cpp); what
+// touches a table or the device is here.
 //
 // Planner semantics (all exact; a leaf the index cannot answer exactly is built from the raw
 // column — by the candidate check of its bin, or by K0 — never approximated):
@@ -688,290 +690,6 @@ int cubit_build_bitvector(cubit_ctx* ctx, const void* d_col, int type, const uin
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ program compilation
-
-namespace {
-
-// Expression over bitvectors. Leaves carry the row predicate they encode so that MVCC
-// update patches can recompute a row's bit from its visible value.
-struct Leaf {
-    const uint64_t* bv = nullptr;
-    int column = -1;  // -1: not derived from a column value (visibility, temp)
-    int pred = 0;     // 0 = cmp (v CMP c), 1 = valid (NN), 2 = bin (c <= v < constant2)
-    int cmp = 0;
-    int64_t constant = 0;
-    int64_t constant2 = 0;
-    // where its zone classes (zonemaps) come from: kZoneBits = bv is a table-owned index leaf or
-    // validity bitvector, classified from its own bits; kZoneStats = bv holds exactly the valid
-    // rows whose base value passes (cmp, constant) — a K0 or candidate-check leaf — classified
-    // from the column's per-zone min / max like a ConstantFilter's CheckStatistics; kZoneNone
-    // = visibility and materialised leaves (mixed everywhere)
-    int zsrc = 0;
-    // a leaf patched with MVCC updates keeps the classes of the base leaf it was copied from
-    // (zbv: that bitvector, for kZoneBits) except in the zones that hold an update record of
-    // column zdirty (there: mixed)
-    const uint64_t* zbv = nullptr;
-    int zdirty = -1;
-};
-enum { kZoneNone = 0, kZoneBits = 1, kZoneStats = 2 };
-
-struct Expr;
-using ExprP = std::shared_ptr<Expr>;
-struct Expr {
-    enum Kind { LEAF, AND, OR, ANDNOT, CONST_TRUE, CONST_FALSE } kind = CONST_FALSE;
-    Leaf leaf;
-    bool neg = false;  // LEAF only
-    ExprP a, b;
-};
-
-ExprP mk_true() {
-    auto e = std::make_shared<Expr>();
-    e->kind = Expr::CONST_TRUE;
-    return e;
-}
-ExprP mk_false() {
-    auto e = std::make_shared<Expr>();
-    e->kind = Expr::CONST_FALSE;
-    return e;
-}
-ExprP mk_leaf(const Leaf& l, bool neg = false) {
-    auto e = std::make_shared<Expr>();
-    e->kind = Expr::LEAF;
-    e->leaf = l;
-    e->neg = neg;
-    return e;
-}
-ExprP mk_not(const ExprP& x);
-ExprP mk_bin(Expr::Kind k, ExprP a, ExprP b) {
-    using K = Expr::Kind;
-    const bool at = a->kind == K::CONST_TRUE, af = a->kind == K::CONST_FALSE;
-    const bool bt = b->kind == K::CONST_TRUE, bf = b->kind == K::CONST_FALSE;
-    switch (k) {
-    case K::AND:
-        if (af || bf) return mk_false();
-        if (at) return b;
-        if (bt) return a;
-        break;
-    case K::OR:
-        if (at || bt) return mk_true();
-        if (af) return b;
-        if (bf) return a;
-        break;
-    case K::ANDNOT:
-        if (af || bt) return mk_false();
-        if (bf) return a;
-        if (at) return mk_not(b);
-        break;
-    default:
-        break;
-    }
-    auto e = std::make_shared<Expr>();
-    e->kind = k;
-    e->a = std::move(a);
-    e->b = std::move(b);
-    return e;
-}
-// NOT pushed to the leaves (De Morgan); ANDNOT(a,b) = a & ~b → ~a | b
-ExprP mk_not(const ExprP& x) {
-    using K = Expr::Kind;
-    switch (x->kind) {
-    case K::CONST_TRUE: return mk_false();
-    case K::CONST_FALSE: return mk_true();
-    case K::LEAF: return mk_leaf(x->leaf, !x->neg);
-    case K::AND: return mk_bin(K::OR, mk_not(x->a), mk_not(x->b));
-    case K::OR: return mk_bin(K::AND, mk_not(x->a), mk_not(x->b));
-    case K::ANDNOT: return mk_bin(K::OR, mk_not(x->a), x->b);
-    }
-    return mk_false();
-}
-
-int count_leaves(const ExprP& e) {
-    if (e->kind == Expr::LEAF) return 1;
-    if (e->kind == Expr::CONST_TRUE || e->kind == Expr::CONST_FALSE) return 0;
-    return count_leaves(e->a) + count_leaves(e->b);
-}
-
-// registers the expression needs (Sethi–Ullman / Strahler number)
-int need(const ExprP& e) {
-    if (e->kind == Expr::LEAF) return 1;
-    const int l = need(e->a), r = need(e->b);
-    return l == r ? l + 1 : std::max(l, r);
-}
-
-// Emit postfix. For AND/OR the heavier child goes first; ANDNOT with a heavier right child
-// is rewritten as AND(~b-side-first) via a reverse op: we keep a & ~b by emitting b first
-// and using AND with the complement pushed into b when b is a leaf, otherwise the order is
-// kept (depth checked by the caller).
-struct Emitter {
-    EvalProgram prog{};
-    int n_ops = 0;
-    int depth = 0, max_depth = 0;
-    bool ok = true;
-    void leaf(const Leaf& l, bool neg) {
-        if (prog.n_leaves >= (uint32_t)kMaxLeaves) {
-            ok = false;
-            return;
-        }
-        const uint32_t k = prog.n_leaves++;
-        prog.leaf[k] = l.bv;
-        if (neg) prog.negate |= 1u << k;
-        max_depth = std::max(max_depth, ++depth);
-    }
-    void op(uint32_t o) {
-        const uint32_t k = prog.n_leaves - 1;
-        if (prog.n_leaves == 0 || n_ops >= kMaxOps || prog_nops(prog, (int)k) == 15) {
-            ok = false;
-            return;
-        }
-        prog.ops |= o << (2 * n_ops++);
-        prog.nops += 1u << (4 * k);
-        --depth;
-    }
-    // a conjunction of (possibly complemented) leaves: AND nodes, ANDNOT with a leaf on the right
-    static bool conj_leaves(const ExprP& e, std::vector<std::pair<Leaf, bool>>& out) {
-        switch (e->kind) {
-        case Expr::LEAF: out.push_back({e->leaf, e->neg}); return true;
-        case Expr::AND: return conj_leaves(e->a, out) && conj_leaves(e->b, out);
-        case Expr::ANDNOT:
-            if (e->b->kind != Expr::LEAF) return false;
-            if (!conj_leaves(e->a, out)) return false;
-            out.push_back({e->b->leaf, !e->b->neg});
-            return true;
-        default: return false;
-        }
-    }
-    using Lits = std::vector<std::pair<Leaf, bool>>;
-    static bool or_literals(const ExprP& e, Lits& out) {
-        if (e->kind == Expr::LEAF) {
-            out.push_back({e->leaf, e->neg});
-            return true;
-        }
-        if (e->kind == Expr::OR) return or_literals(e->a, out) && or_literals(e->b, out);
-        return false;
-    }
-    static void or_parts(const ExprP& e, std::vector<ExprP>& out) {
-        if (e->kind == Expr::OR) {
-            or_parts(e->a, out);
-            or_parts(e->b, out);
-        } else {
-            out.push_back(e);
-        }
-    }
-    // AND-ed parts; a & ~leaf contributes the complemented leaf as a part of its own
-    static bool and_parts(const ExprP& e, std::vector<Lits>& groups) {
-        if (e->kind == Expr::AND) return and_parts(e->a, groups) && and_parts(e->b, groups);
-        if (e->kind == Expr::ANDNOT) {
-            if (e->b->kind != Expr::LEAF) return false;
-            if (!and_parts(e->a, groups)) return false;
-            groups.push_back({{e->b->leaf, !e->b->neg}});
-            return true;
-        }
-        Lits g;
-        if (!or_literals(e, g)) return false;
-        groups.push_back(std::move(g));
-        return true;
-    }
-    // two-level program: groups of literals combined by `inner`, groups combined by `outer`;
-    // the postfix encoding of the same program is emitted alongside (interpreter fallback)
-    bool emit_groups(const std::vector<Lits>& groups, uint32_t inner, uint32_t outer, uint32_t form) {
-        size_t total = 0;
-        for (const auto& g : groups) total += g.size();
-        if (groups.empty() || total > (size_t)kMaxLeaves) return false;
-        uint32_t gstart = 0;
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-            gstart |= 1u << prog.n_leaves;
-            for (size_t i = 0; i < groups[gi].size(); ++i) {
-                leaf(groups[gi][i].first, groups[gi][i].second);
-                if (i) op(inner);
-            }
-            if (gi) op(outer);
-        }
-        prog.form = form;
-        prog.gstart = gstart;
-        return ok;
-    }
-    // top level: a pure conjunction is emitted as a left-deep AND chain (branch-free CONJ
-    // form, is_conjunction in cubit_kernels.hip); an OR of conjunctions (DNF) or an AND of
-    // ORs of literals (CNF) as a branch-free two-level program; anything else as postfix
-    void emit_top(const ExprP& e) {
-        Lits c;
-        if (e->kind != Expr::LEAF && conj_leaves(e, c)) {
-            leaf(c[0].first, c[0].second);
-            for (size_t i = 1; i < c.size(); ++i) {
-                leaf(c[i].first, c[i].second);
-                op(OP_AND);
-            }
-            return;
-        }
-        if (e->kind == Expr::OR) {
-            std::vector<ExprP> parts;
-            or_parts(e, parts);
-            std::vector<Lits> groups;
-            bool dnf = true;
-            for (const auto& p : parts) {
-                Lits g;
-                if (!conj_leaves(p, g)) {
-                    dnf = false;
-                    break;
-                }
-                groups.push_back(std::move(g));
-            }
-            if (dnf) {
-                Emitter trial;
-                if (trial.emit_groups(groups, OP_AND, OP_OR, FORM_DNF)) {
-                    *this = trial;
-                    return;
-                }
-            }
-        }
-        if (e->kind == Expr::AND || e->kind == Expr::ANDNOT) {
-            std::vector<Lits> groups;
-            if (and_parts(e, groups)) {
-                Emitter trial;
-                if (trial.emit_groups(groups, OP_OR, OP_AND, FORM_CNF)) {
-                    *this = trial;
-                    return;
-                }
-            }
-        }
-        emit(e);
-    }
-    void emit(const ExprP& e) {
-        switch (e->kind) {
-        case Expr::LEAF: leaf(e->leaf, e->neg); return;
-        case Expr::AND:
-        case Expr::OR: {
-            const uint32_t o = e->kind == Expr::AND ? OP_AND : OP_OR;
-            if (need(e->b) > need(e->a)) {
-                emit(e->b);
-                emit(e->a);
-            } else {
-                emit(e->a);
-                emit(e->b);
-            }
-            op(o);
-            return;
-        }
-        case Expr::ANDNOT: {
-            if (need(e->b) > need(e->a) && e->b->kind == Expr::LEAF) {
-                // a & ~b == (~b) & a with b a leaf: emit complemented leaf first
-                leaf(e->b->leaf, !e->b->neg);
-                emit(e->a);
-                op(OP_AND);
-            } else {
-                emit(e->a);
-                emit(e->b);
-                op(OP_ANDNOT);
-            }
-            return;
-        }
-        default: ok = false; return;
-        }
-    }
-};
-
-}  // namespace
-
 extern "C" int cubit_bitvector_eval(cubit_ctx* ctx, const uint64_t* const* d_leaves, uint32_t n_leaves,
                                     uint32_t leaf_negate, const int32_t* prog, uint32_t n_prog, uint64_t n_rows,
                                     int64_t row_base, int64_t* d_rowids, uint64_t capacity, uint64_t* d_count,
@@ -986,38 +704,20 @@ extern "C" int cubit_bitvector_eval(cubit_ctx* ctx, const uint64_t* const* d_lea
     }
     const bool count_only = (flags & CUBIT_SCAN_COUNT_ONLY) != 0;
     if (!count_only && !d_rowids) return fail(CUBIT_ERR_INVALID, "d_rowids is null without COUNT_ONLY");
-    // postfix → expression (validates arity), then the emitter re-linearises it
-    std::vector<ExprP> st;
-    for (uint32_t i = 0; i < n_prog; ++i) {
-        const int32_t x = prog[i];
-        if (x >= 0) {
-            if ((uint32_t)x >= n_leaves) return fail(CUBIT_ERR_INVALID, "leaf %d out of range", x);
-            Leaf l;
-            l.bv = d_leaves[x];
-            st.push_back(mk_leaf(l, ((leaf_negate >> x) & 1u) != 0));
-        } else {
-            if (st.size() < 2) return fail(CUBIT_ERR_INVALID, "program underflow at %u", i);
-            ExprP b = st.back();
-            st.pop_back();
-            ExprP a = st.back();
-            st.pop_back();
-            Expr::Kind k = x == CUBIT_OP_AND ? Expr::AND : x == CUBIT_OP_OR ? Expr::OR : x == CUBIT_OP_ANDNOT
-                                                                                         ? Expr::ANDNOT
-                                                                                         : Expr::CONST_FALSE;
-            if (k == Expr::CONST_FALSE) return fail(CUBIT_ERR_INVALID, "bad opcode %d", x);
-            auto e = std::make_shared<Expr>();
-            e->kind = k;
-            e->a = a;
-            e->b = b;
-            st.push_back(e);
-        }
+    // postfix → expression (parse_postfix validates arity), then the emitter re-linearises it
+    const PostfixParse pp = parse_postfix(d_leaves, n_leaves, leaf_negate, prog, n_prog);
+    switch (pp.error) {
+    case PostfixParse::kNone: break;
+    case PostfixParse::kLeafRange: return fail(CUBIT_ERR_INVALID, "leaf %d out of range", pp.value);
+    case PostfixParse::kUnderflow: return fail(CUBIT_ERR_INVALID, "program underflow at %u", pp.at);
+    case PostfixParse::kBadOpcode: return fail(CUBIT_ERR_INVALID, "bad opcode %d", pp.value);
+    default: return fail(CUBIT_ERR_INVALID, "program leaves %zu values on the stack", pp.left);
     }
-    if (st.size() != 1) return fail(CUBIT_ERR_INVALID, "program leaves %zu values on the stack", st.size());
     Emitter em;
-    em.emit_top(st[0]);
-    if (!em.ok || em.max_depth > 4)
-        return fail(CUBIT_ERR_UNSUPPORTED, "program needs %d leaves / depth %d (max %d / 4)", count_leaves(st[0]),
-                    em.max_depth, kMaxLeaves);
+    em.emit_top(pp.expr);
+    if (!em.ok || em.max_depth > kMaxDepth)
+        return fail(CUBIT_ERR_UNSUPPORTED, "program needs %d leaves / depth %d (max %d / %d)", count_leaves(pp.expr),
+                    em.max_depth, kMaxLeaves, kMaxDepth);
     return run_eval(ctx, em.prog, n_rows, row_base, count_only ? nullptr : d_rowids, capacity, d_count, d_result_words,
                     count_only ? RunMode::kCount : RunMode::kDecode, true, (flags & CUBIT_SCAN_ORDERED) != 0,
                     (flags & CUBIT_SCAN_CHECK_CAPACITY) != 0);
@@ -3224,22 +2924,30 @@ int compute_k0(cubit_table* t, const PendingK0& k) {
     return CUBIT_OK;
 }
 
+// A filter node against the table: its kind, its column registered, its comparison.
+int check_node(const cubit_table* t, const cubit_filter_node& f) {
+    const NodeCheck c = check_filter_node(f);
+    if (c == NodeCheck::kBadKind) return fail(CUBIT_ERR_INVALID, "filter node kind %d", f.kind);
+    if (f.kind != CUBIT_FILTER_OR && f.kind != CUBIT_FILTER_AND && !t->cols.count(f.column))
+        return fail(CUBIT_ERR_INVALID, "filter references unregistered column %d", f.column);
+    if (c == NodeCheck::kBadCmp) return fail(CUBIT_ERR_INVALID, "comparison %d", f.cmp);
+    return CUBIT_OK;
+}
+
+// An inclusive range as the half-open bounds lo <= v < hi that interval_from_bins and eq_interval
+// take, either side open: no bound where the range reaches the end of INT64.
+struct HalfOpen {
+    int64_t lo, hi;
+    bool has_lo, has_hi;
+    explicit HalfOpen(const CmpRange& r)
+        : lo(r.lo), hi(r.hi == INT64_MAX ? r.hi : r.hi + 1), has_lo(r.lo != INT64_MIN), has_hi(r.hi != INT64_MAX) {}
+};
+
 struct Planner {
     cubit_table* t;
     const cubit_filter_node* nodes;
     uint32_t n_nodes;
     int rc = CUBIT_OK;
-
-    int subtree_end(uint32_t i) {
-        if (i >= n_nodes) return -1;
-        uint32_t j = i + 1;
-        for (int k = 0; k < nodes[i].n_children; ++k) {
-            int e = subtree_end(j);
-            if (e < 0) return -1;
-            j = (uint32_t)e;
-        }
-        return (int)j;
-    }
 
     ExprP nn(int col) {
         const Column& c = t->cols.at(col);
@@ -3428,16 +3136,11 @@ struct Planner {
                 } else if (ix.exact_all) {
                     // the equality bitvectors in range, or the valid rows outside the others
                     // (whichever reads fewer); wide ranges both ways go to K0
-                    const bool has_lo = cmp == CUBIT_CMP_GT || cmp == CUBIT_CMP_GE;
-                    int64_t lo = 0, hi = 0;
-                    bool empty = false;
-                    if (cmp == CUBIT_CMP_GE) lo = c;
-                    else if (cmp == CUBIT_CMP_GT) empty = c == INT64_MAX, lo = empty ? c : c + 1;
-                    else if (cmp == CUBIT_CMP_LT) hi = c;
-                    else if (c == INT64_MAX) return nn(col);
-                    else hi = c + 1;
-                    if (empty) return mk_false();
-                    if (ExprP e = eq_interval(col, ix, lo, hi, has_lo, !has_lo)) return e;
+                    const CmpRange r = cmp_range(cmp, c, 0);
+                    if (r.empty()) return mk_false();
+                    if (cmp == CUBIT_CMP_LE && top) return nn(col);
+                    const HalfOpen h(r);
+                    if (ExprP e = eq_interval(col, ix, h.lo, h.hi, h.has_lo, h.has_hi)) return e;
                 }
             }
         }
@@ -3493,11 +3196,7 @@ struct Planner {
     // pushes "a <= x AND x < b" as one ConjunctionAndFilter on x, table_filter.cpp:20-40).
     ExprP plan_and(uint32_t i) {
         const cubit_filter_node& f = nodes[i];
-        struct Bounds {
-            int64_t lo = INT64_MIN, hi = INT64_MAX;
-            bool has_lo = false, has_hi = false, empty = false;
-            std::vector<uint32_t> members;
-        };
+        struct Bounds { CmpRange r; std::vector<uint32_t> members; };
         std::map<int, Bounds> by_col;
         std::vector<uint32_t> kids;
         uint32_t j = i + 1;
@@ -3507,35 +3206,23 @@ struct Planner {
             if (c.kind == CUBIT_FILTER_CONSTANT && c.n_children == 0 && c.cmp != CUBIT_CMP_NE && c.cmp >= 0 &&
                 c.cmp <= 5 && (t->bins.count(c.column) || exact_equality(c.column))) {
                 Bounds& bd = by_col[c.column];
-                const int64_t v = c.constant;
-                auto lower = [&](int64_t x) { bd.lo = bd.has_lo ? std::max(bd.lo, x) : x; bd.has_lo = true; };
-                auto upper = [&](int64_t x) { bd.hi = bd.has_hi ? std::min(bd.hi, x) : x; bd.has_hi = true; };
-                switch (c.cmp) {
-                case CUBIT_CMP_GE: lower(v); break;
-                case CUBIT_CMP_GT: if (v == INT64_MAX) bd.empty = true; else lower(v + 1); break;
-                case CUBIT_CMP_LT: upper(v); break;
-                case CUBIT_CMP_LE: if (v != INT64_MAX) upper(v + 1); break;
-                case CUBIT_CMP_EQ:  // [v, v + 1); v = INT64_MAX: [v, ∞) is {v} (a UBIGINT 2^64 - 1's key)
-                    lower(v);
-                    if (v != INT64_MAX) upper(v + 1);
-                    break;
-                default: break;
-                }
+                bd.r = bd.r.intersect(cmp_range(c.cmp, c.constant, 0));
                 bd.members.push_back(j);
             }
-            j = (uint32_t)subtree_end(j);
+            j = (uint32_t)filter_subtree_end(nodes, n_nodes, j);
         }
         std::vector<char> done(n_nodes, 0);
         ExprP acc = mk_true();
         for (auto& [col, bd] : by_col) {
             ExprP e;
-            if (bd.empty || (bd.has_lo && bd.has_hi && bd.hi <= bd.lo)) e = mk_false();
-            else if (t->bins.count(col)) e = interval_from_bins(col, bd.lo, bd.hi, bd.has_lo, bd.has_hi);
+            const HalfOpen h(bd.r);
+            if (bd.r.empty()) e = mk_false();
+            else if (t->bins.count(col)) e = interval_from_bins(col, h.lo, h.hi, h.has_lo, h.has_hi);
             if (!e && !rc && bd.members.size() > 1) {
                 // two or more bounds on an every-value equality index: one union for the interval
                 if (const Index* eq = exact_equality(col)) {
                     const IndexView v = view_of(t, col, *eq);  // exact only while every updated value is a key
-                    if (v.exact_all && !v.empty) e = eq_interval(col, v, bd.lo, bd.hi, bd.has_lo, bd.has_hi);
+                    if (v.exact_all && !v.empty) e = eq_interval(col, v, h.lo, h.hi, h.has_lo, h.has_hi);
                 }
             }
             if (rc) return nullptr;
@@ -3555,6 +3242,7 @@ struct Planner {
     ExprP plan(uint32_t i) {
         if (rc) return nullptr;
         const cubit_filter_node& f = nodes[i];
+        if ((rc = check_node(t, f))) return nullptr;
         switch (f.kind) {
         case CUBIT_FILTER_AND:
             return plan_and(i);
@@ -3565,28 +3253,13 @@ struct Planner {
                 ExprP c = plan(j);
                 if (!c) return nullptr;
                 acc = mk_bin(Expr::OR, acc, c);
-                j = (uint32_t)subtree_end(j);
+                j = (uint32_t)filter_subtree_end(nodes, n_nodes, j);
             }
             return acc;
         }
-        case CUBIT_FILTER_CONSTANT:
-        case CUBIT_FILTER_IS_NULL:
-        case CUBIT_FILTER_IS_NOT_NULL: {
-            if (!t->cols.count(f.column)) {
-                rc = fail(CUBIT_ERR_INVALID, "filter references unregistered column %d", f.column);
-                return nullptr;
-            }
-            if (f.kind == CUBIT_FILTER_IS_NOT_NULL) return nn(f.column);
-            if (f.kind == CUBIT_FILTER_IS_NULL) return mk_not(nn(f.column));
-            if (f.cmp < 0 || f.cmp > 5) {
-                rc = fail(CUBIT_ERR_INVALID, "comparison %d", f.cmp);
-                return nullptr;
-            }
-            return constant(f.column, f.cmp, f.constant);
-        }
-        default:
-            rc = fail(CUBIT_ERR_INVALID, "filter node kind %d", f.kind);
-            return nullptr;
+        case CUBIT_FILTER_IS_NOT_NULL: return nn(f.column);
+        case CUBIT_FILTER_IS_NULL: return mk_not(nn(f.column));
+        default: return constant(f.column, f.cmp, f.constant);
         }
     }
 };
@@ -3595,36 +3268,16 @@ struct Planner {
 int materialize(cubit_table* t, const ExprP& e, uint64_t** out) {
     Emitter em;
     em.emit_top(e);
-    if (!em.ok || em.max_depth > 4) return fail(CUBIT_ERR_UNSUPPORTED, "subexpression too deep");
+    if (!em.ok || em.max_depth > kMaxDepth) return fail(CUBIT_ERR_UNSUPPORTED, "subexpression too deep");
     if (int rc = scratch_bv(t, out)) return rc;
     t->last_passes++;
     return run_eval(t->ctx, em.prog, t->n_rows, 0, nullptr, 0, t->dummy_count, *out, RunMode::kCount);
 }
 
-bool fits(const ExprP& e);
 int fit(cubit_table* t, ExprP& e);
 double literal_selectivity(cubit_table* t, const Leaf& l, bool neg, int* rc);
 double conj_selectivity(cubit_table* t, const Emitter::Lits& lits, int* rc);
 
-// top-level conjuncts of e (a & ~leaf contributes the complemented leaf as a conjunct)
-void conj_parts(const ExprP& e, std::vector<ExprP>& out) {
-    if (e->kind == Expr::AND) {
-        conj_parts(e->a, out);
-        conj_parts(e->b, out);
-    } else if (e->kind == Expr::ANDNOT && e->b->kind == Expr::LEAF) {
-        conj_parts(e->a, out);
-        out.push_back(mk_leaf(e->b->leaf, !e->b->neg));
-    } else if (e->kind != Expr::CONST_TRUE) {
-        out.push_back(e);
-    }
-}
-void leaves_of(const ExprP& e, std::vector<const uint64_t*>& out) {
-    if (e->kind == Expr::LEAF) out.push_back(e->leaf.bv);
-    else if (e->a) {
-        leaves_of(e->a, out);
-        if (e->b) leaves_of(e->b, out);
-    }
-}
 // estimated fraction of rows a subtree keeps, from its literals' estimates
 double expr_selectivity(cubit_table* t, const ExprP& e, int* rc) {
     switch (e->kind) {
@@ -3781,12 +3434,6 @@ int narrow_k0(cubit_table* t, ExprP& e, std::vector<PendingK0>& pending, bool al
     ml.bv = mask;
     e = mk_leaf(ml);
     return compute_rest();
-}
-
-bool fits(const ExprP& e) {
-    Emitter em;
-    em.emit_top(e);
-    return em.ok && em.max_depth <= 4;
 }
 
 // Reduce an expression until it fits one kernel pass (<= kMaxLeaves leaves, depth <= 4):
@@ -4424,17 +4071,9 @@ extern "C" int cubit_table_estimate_rows(cubit_table* t, const cubit_filter_node
     CUBIT_LOCK(t->ctx);
     *rows = t->n_rows;
     if (n_nodes == 0 || t->n_rows == 0) return CUBIT_OK;
-    Planner shape{t, nodes, n_nodes};
-    if (shape.subtree_end(0) != (int)n_nodes) return fail(CUBIT_ERR_INVALID, "malformed filter tree");
-    for (uint32_t k = 0; k < n_nodes; ++k) {
-        const cubit_filter_node& f = nodes[k];
-        if (f.kind < CUBIT_FILTER_CONSTANT || f.kind > CUBIT_FILTER_AND)
-            return fail(CUBIT_ERR_INVALID, "filter node kind %d", f.kind);
-        if (f.kind != CUBIT_FILTER_OR && f.kind != CUBIT_FILTER_AND && !t->cols.count(f.column))
-            return fail(CUBIT_ERR_INVALID, "filter references unregistered column %d", f.column);
-        if (f.kind == CUBIT_FILTER_CONSTANT && (f.cmp < 0 || f.cmp > 5))
-            return fail(CUBIT_ERR_INVALID, "comparison %d", f.cmp);
-    }
+    if (filter_subtree_end(nodes, n_nodes, 0) != (int)n_nodes) return fail(CUBIT_ERR_INVALID, "malformed filter tree");
+    for (uint32_t k = 0; k < n_nodes; ++k)
+        if (int rc = check_node(t, nodes[k])) return rc;
     if (int rc = set_device(t->ctx)) return rc;
     int rc = CUBIT_OK;
     uint32_t i = 0;
@@ -4471,8 +4110,9 @@ int plan_program(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_node
     } else {
         const KeyedNodes keyed(t, nodes, n_nodes);
         if (keyed.rc) return keyed.rc;
+        if (filter_subtree_end(keyed.p, n_nodes, 0) != (int)n_nodes)
+            return fail(CUBIT_ERR_INVALID, "malformed filter tree");
         Planner p{t, keyed.p, n_nodes};
-        if (p.subtree_end(0) != (int)n_nodes) return fail(CUBIT_ERR_INVALID, "malformed filter tree");
         e = p.plan(0);
         if (!e) return p.rc ? p.rc : fail(CUBIT_ERR_INVALID, "planning failed");
         pending = std::move(p.pending);
@@ -4628,11 +4268,12 @@ bool decodable_values(cubit_table* t, const cubit_filter_node* nodes, uint32_t n
     if (ixit == t->idx.end() || n_nodes == 0) return false;
     const IndexView ix = view_of(t, col, ixit->second);
     if (ix.encoding != CUBIT_INDEX_RANGE || !ix.exact_all || ix.empty) return false;
-    int64_t lo = ix.vmin, hi = ix.vmax;  // inclusive bounds
+    CmpRange r;  // the column's values, narrowed by every bound
+    r.lo = ix.vmin;
+    r.hi = ix.vmax;
     bool bounded = false;
     // constants on col reachable through AND nodes only
     std::vector<uint32_t> stack{0};
-    Planner pl{t, nodes, n_nodes};
     while (!stack.empty()) {
         const uint32_t i = stack.back();
         stack.pop_back();
@@ -4641,27 +4282,20 @@ bool decodable_values(cubit_table* t, const cubit_filter_node* nodes, uint32_t n
             uint32_t j = i + 1;
             for (int k = 0; k < f.n_children; ++k) {
                 stack.push_back(j);
-                j = (uint32_t)pl.subtree_end(j);
+                j = (uint32_t)filter_subtree_end(nodes, n_nodes, j);
             }
         } else if (f.kind == CUBIT_FILTER_CONSTANT && f.column == col) {
-            const int64_t c = f.constant;
-            switch (f.cmp) {
-            case CUBIT_CMP_EQ: lo = std::max(lo, c); hi = std::min(hi, c); break;
-            case CUBIT_CMP_LT: if (c == INT64_MIN) return false; hi = std::min(hi, c - 1); break;
-            case CUBIT_CMP_LE: hi = std::min(hi, c); break;
-            case CUBIT_CMP_GT: if (c == INT64_MAX) return false; lo = std::max(lo, c + 1); break;
-            case CUBIT_CMP_GE: lo = std::max(lo, c); break;
-            default: continue;
-            }
+            if (f.cmp == CUBIT_CMP_NE || check_filter_node(f) != NodeCheck::kOk) continue;
+            r = r.intersect(cmp_range(f.cmp, f.constant, 0));  // < INT64_MIN, > INT64_MAX: empty, refused below
             bounded = true;
         }
     }
-    if (!bounded || lo > hi) return false;
+    if (!bounded || r.empty()) return false;
     vals.clear();
     leaves.clear();
-    if (ix.vmin >= lo && ix.vmin <= hi) vals.push_back(ix.vmin);
+    if (r.contains(ix.vmin)) vals.push_back(ix.vmin);
     for (size_t k = 0; k < ix.keys.size(); ++k) {
-        if (ix.keys[k] < lo || ix.keys[k] > hi) continue;
+        if (!r.contains(ix.keys[k])) continue;
         if (!vals.empty()) leaves.push_back(ix.bvs[k]);  // L(v_j) for j >= 1
         vals.push_back(ix.keys[k]);
         if (vals.size() > (size_t)kMaxDecode + 1) return false;

@@ -6,6 +6,7 @@
 
 #include <cstdint>
 
+#include "cubit_program.hpp"
 #include "cubit_segments.hpp"
 
 namespace cubit {
@@ -23,31 +24,7 @@ static_assert(kRowGroupSize % 64 == 0 && kRowGroupSize / 64 == 1920, "row group 
 // to kPadWords so every tile shape reads in bounds.
 constexpr int kThreads = 256;
 constexpr uint64_t kPadWords = 16384;  // 1,048,576 rows
-constexpr int kMaxLeaves = 8;
-constexpr int kMaxOps = 16;  // 2 bits each in EvalProgram::ops
-
-enum : uint32_t { OP_AND = 1, OP_OR = 2, OP_ANDNOT = 3 };
-
-// A postfix program whose leaves appear in order 0..n_leaves-1: leaf k is pushed
-// (complemented if bit k of `negate`), then nops(k) binary ops are applied. The op counts
-// (4 bits per leaf) and opcodes (2 bits per op) are packed into words so the kernel decodes
-// them with scalar shifts (a runtime-indexed byte array in the kernel arguments compiles to
-// vector loads, each followed by an s_waitcnt vmcnt(0) that drains every outstanding load).
-// Evaluation forms: the general postfix interpreter, or a branch-free two-level form chosen
-// by the planner's emitter (leaves ordered by group, gstart bit k = leaf k opens a group).
-enum : uint32_t { FORM_POSTFIX = 0, FORM_CONJ = 1, FORM_DNF = 2, FORM_CNF = 3 };
-
-struct EvalProgram {
-    const uint64_t* leaf[kMaxLeaves];
-    uint32_t negate;
-    uint32_t n_leaves;
-    uint32_t nops;    // 4 bits per leaf
-    uint32_t ops;     // 2 bits per op
-    uint32_t form;    // FORM_*; FORM_POSTFIX runs the postfix program (is_conjunction upgrades)
-    uint32_t gstart;  // FORM_DNF / FORM_CNF group starts
-};
-
-inline uint32_t prog_nops(const EvalProgram& p, int k) { return (p.nops >> (4 * k)) & 15u; }
+// kMaxLeaves, EvalProgram and the evaluation forms: cubit_program.hpp
 
 // Column value types as the kernels see them: INT32 / INT64 values, or FLOAT / DOUBLE bit patterns
 // (4 / 8 bytes) compared through their order key (cubit_fp_key, include/cubit_gpu.h: NaN one key

@@ -3483,17 +3483,23 @@ uint64_t decode_tile_words() { return (uint64_t)kDecodeThreads * 2 * kDecodePair
 uint64_t count_tile_words(uint32_t n_leaves) { return 512ull * 2 * (uint64_t)count_pairs(n_leaves); }
 int decode_block_threads() { return kDecodeThreads; }
 
-// A left-deep chain of ANDs (nops = 0,1,1,…; every op AND) evaluates as a plain conjunction.
-bool is_conjunction(const EvalProgram& p) {
-    if (p.n_leaves == 0 || prog_nops(p, 0) != 0) return false;
-    for (uint32_t k = 1; k < p.n_leaves; ++k)
-        if (prog_nops(p, (int)k) != 1 || ((p.ops >> (2 * (k - 1))) & 3u) != OP_AND) return false;
-    return true;
-}
-
-uint32_t eval_form(const EvalProgram& p) {
-    if (p.form == FORM_DNF || p.form == FORM_CNF || p.form == FORM_CONJ) return p.form;
-    return is_conjunction(p) ? FORM_CONJ : FORM_POSTFIX;
+// K × FORM dispatch: f(K, FORM), both std::integral_constant, for a program of 1 … kMaxLeaves leaves
+// and the form eval_form gives it; any other leaf count: no call, hipErrorInvalidValue.
+template <int K = 1, typename F>
+hipError_t dispatch_k_form(const EvalProgram& prog, const F& f) {
+    using KC = std::integral_constant<int, K>;
+    if constexpr (K > kMaxLeaves) {
+        return hipErrorInvalidValue;
+    } else {
+        if (prog.n_leaves != (uint32_t)K) return dispatch_k_form<K + 1>(prog, f);
+        switch (eval_form(prog)) {
+        case FORM_CONJ: f(KC{}, std::integral_constant<int, FORM_CONJ>{}); break;
+        case FORM_DNF: f(KC{}, std::integral_constant<int, FORM_DNF>{}); break;
+        case FORM_CNF: f(KC{}, std::integral_constant<int, FORM_CNF>{}); break;
+        default: f(KC{}, std::integral_constant<int, FORM_POSTFIX>{}); break;
+        }
+        return hipSuccess;
+    }
 }
 
 // production decode (scripts/kbench.hip): the run-claimed kernel wherever a
@@ -3538,18 +3544,6 @@ void launch_decode_kf(const EvalArgs& a, uint64_t* dir, unsigned grid, hipStream
                               dim3(kDecodeThreads), 0, s, e0, e1, 0, a, dir);
 }
 
-template <int K>
-hipError_t launch_decode_k(const EvalArgs& a, uint64_t* dir, unsigned grid, hipStream_t s, hipEvent_t e0,
-                           hipEvent_t e1, int kernel, int n_cus) {
-    switch (eval_form(a.prog)) {
-    case FORM_CONJ: launch_decode_kf<K, FORM_CONJ>(a, dir, grid, s, e0, e1, kernel, n_cus); break;
-    case FORM_DNF: launch_decode_kf<K, FORM_DNF>(a, dir, grid, s, e0, e1, kernel, n_cus); break;
-    case FORM_CNF: launch_decode_kf<K, FORM_CNF>(a, dir, grid, s, e0, e1, kernel, n_cus); break;
-    default: launch_decode_kf<K, FORM_POSTFIX>(a, dir, grid, s, e0, e1, kernel, n_cus); break;
-    }
-    return hipGetLastError();
-}
-
 template <int K, int FORM>
 void launch_count_kf(const EvalArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const unsigned grid = std::min<unsigned>(a.num_tiles, (unsigned)kCountGrid);
@@ -3559,48 +3553,23 @@ void launch_count_kf(const EvalArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t
     hipExtLaunchKernelGGL((eval_count_kernel<K, count_pairs(K), FORM>), dim3(grid), dim3(512), 0, s, e0, e1, 0, a);
 }
 
-template <int K>
-hipError_t launch_count_k(const EvalArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    switch (eval_form(a.prog)) {
-    case FORM_CONJ: launch_count_kf<K, FORM_CONJ>(a, s, e0, e1); break;
-    case FORM_DNF: launch_count_kf<K, FORM_DNF>(a, s, e0, e1); break;
-    case FORM_CNF: launch_count_kf<K, FORM_CNF>(a, s, e0, e1); break;
-    default: launch_count_kf<K, FORM_POSTFIX>(a, s, e0, e1); break;
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_eval_decode(const EvalArgs& a, uint64_t* dir, unsigned grid, hipStream_t s, hipEvent_t e0,
                               hipEvent_t e1, int kernel, int n_cus) {
     if (decode_kernel_for(a.prog.n_leaves, a.num_tiles, grid, kernel, a.live != nullptr, n_cus,
                           a.tile_prefix != nullptr) == 3 &&
         (a.num_tiles == 0 || (!a.tile_prefix && (a.flags == nullptr || a.epoch == 0))))
         return hipErrorInvalidValue;  // the look-back kernel needs the context's flags and an epoch
-    switch (a.prog.n_leaves) {
-    case 1: return launch_decode_k<1>(a, dir, grid, s, e0, e1, kernel, n_cus);
-    case 2: return launch_decode_k<2>(a, dir, grid, s, e0, e1, kernel, n_cus);
-    case 3: return launch_decode_k<3>(a, dir, grid, s, e0, e1, kernel, n_cus);
-    case 4: return launch_decode_k<4>(a, dir, grid, s, e0, e1, kernel, n_cus);
-    case 5: return launch_decode_k<5>(a, dir, grid, s, e0, e1, kernel, n_cus);
-    case 6: return launch_decode_k<6>(a, dir, grid, s, e0, e1, kernel, n_cus);
-    case 7: return launch_decode_k<7>(a, dir, grid, s, e0, e1, kernel, n_cus);
-    case 8: return launch_decode_k<8>(a, dir, grid, s, e0, e1, kernel, n_cus);
-    default: return hipErrorInvalidValue;
-    }
+    const hipError_t e = dispatch_k_form(a.prog, [&](auto k, auto form) {
+        launch_decode_kf<k.value, form.value>(a, dir, grid, s, e0, e1, kernel, n_cus);
+    });
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_eval_count(const EvalArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    switch (a.prog.n_leaves) {
-    case 1: return launch_count_k<1>(a, s, e0, e1);
-    case 2: return launch_count_k<2>(a, s, e0, e1);
-    case 3: return launch_count_k<3>(a, s, e0, e1);
-    case 4: return launch_count_k<4>(a, s, e0, e1);
-    case 5: return launch_count_k<5>(a, s, e0, e1);
-    case 6: return launch_count_k<6>(a, s, e0, e1);
-    case 7: return launch_count_k<7>(a, s, e0, e1);
-    case 8: return launch_count_k<8>(a, s, e0, e1);
-    default: return hipErrorInvalidValue;
-    }
+    const hipError_t e = dispatch_k_form(a.prog, [&](auto k, auto form) {
+        launch_count_kf<k.value, form.value>(a, s, e0, e1);
+    });
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_order_runs(const uint64_t* dir, uint32_t n_tiles, uint64_t* dst_off, const int64_t* src,
@@ -3899,40 +3868,19 @@ hipError_t launch_gather_sum_product(const int64_t* x, const int64_t* y, const i
 
 unsigned sum_product_grid(unsigned n_cus) { return std::min<unsigned>(2 * n_cus, (unsigned)kSumBlocks); }
 
-template <int K, int M>
-void launch_sum_km(const EvalArgs& a, const SumArgs& s, unsigned grid, hipStream_t st) {
-    switch (eval_form(a.prog)) {
-    case FORM_CONJ: hipLaunchKernelGGL((eval_sum_product<K, M, FORM_CONJ>), dim3(grid), dim3(512), 0, st, a, s); break;
-    case FORM_DNF: hipLaunchKernelGGL((eval_sum_product<K, M, FORM_DNF>), dim3(grid), dim3(512), 0, st, a, s); break;
-    case FORM_CNF: hipLaunchKernelGGL((eval_sum_product<K, M, FORM_CNF>), dim3(grid), dim3(512), 0, st, a, s); break;
-    default: hipLaunchKernelGGL((eval_sum_product<K, M, FORM_POSTFIX>), dim3(grid), dim3(512), 0, st, a, s); break;
-    }
-}
-
-template <int K>
-void launch_sum_k(const EvalArgs& a, const SumArgs& s, unsigned grid, hipStream_t st) {
-    switch (s.b ? 0 : s.n_decode) {
-    case 0: launch_sum_km<K, 0>(a, s, grid, st); break;
-    case 1: launch_sum_km<K, 1>(a, s, grid, st); break;
-    case 2: launch_sum_km<K, 2>(a, s, grid, st); break;
-    default: launch_sum_km<K, 3>(a, s, grid, st); break;
-    }
-}
-
 hipError_t launch_eval_sum_product(const EvalArgs& a, const SumArgs& s, unsigned grid, int64_t* out, hipStream_t st) {
     if (!s.b && s.n_decode > (uint32_t)kMaxDecode) return hipErrorInvalidValue;
-    switch (a.prog.n_leaves) {
-    case 1: launch_sum_k<1>(a, s, grid, st); break;
-    case 2: launch_sum_k<2>(a, s, grid, st); break;
-    case 3: launch_sum_k<3>(a, s, grid, st); break;
-    case 4: launch_sum_k<4>(a, s, grid, st); break;
-    case 5: launch_sum_k<5>(a, s, grid, st); break;
-    case 6: launch_sum_k<6>(a, s, grid, st); break;
-    case 7: launch_sum_k<7>(a, s, grid, st); break;
-    case 8: launch_sum_k<8>(a, s, grid, st); break;
-    default: return hipErrorInvalidValue;
-    }
-    hipError_t e = hipGetLastError();
+    hipError_t e = dispatch_k_form(a.prog, [&](auto k, auto form) {
+#define CUBIT_SUM(M) hipLaunchKernelGGL((eval_sum_product<k.value, M, form.value>), dim3(grid), dim3(512), 0, st, a, s)
+        switch (s.b ? 0 : s.n_decode) {  // M: the values b is decoded from (0: gathered)
+        case 0: CUBIT_SUM(0); break;
+        case 1: CUBIT_SUM(1); break;
+        case 2: CUBIT_SUM(2); break;
+        default: CUBIT_SUM(3); break;
+        }
+#undef CUBIT_SUM
+    });
+    if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, st, s.partials, (int)grid, out);
     return hipGetLastError();
@@ -4148,34 +4096,6 @@ hipError_t launch_rle_expand(const void* vals, const uint64_t* ends, uint64_t n_
                               static_cast<const int64_t*>(vals), ends, tile_first, n_runs, n_rows,
                               static_cast<int64_t*>(out));
     return hipGetLastError();
-}
-
-// A comparison (CUBIT_CMP_* or kCmpBetween) as the inclusive range [lo, hi] of passing values,
-// complemented when neg (!=); empty: lo > hi. clamp32 narrows it to INT32 values.
-struct CmpRange {
-    int64_t lo = INT64_MIN, hi = INT64_MAX;
-    int neg = 0;
-    void clamp32(int32_t& lo32, int32_t& hi32) const {
-        const bool empty = lo > hi || lo > INT32_MAX || hi < INT32_MIN;
-        lo32 = empty ? 1 : (int32_t)std::max<int64_t>(lo, INT32_MIN);
-        hi32 = empty ? 0 : (int32_t)std::min<int64_t>(hi, INT32_MAX);
-    }
-};
-CmpRange cmp_range(int cmp, int64_t constant, int64_t constant2) {
-    CmpRange r;
-    switch (cmp) {
-    case 0: r.lo = r.hi = constant; break;                                            // =
-    case 1: r.lo = r.hi = constant; r.neg = 1; break;                                 // !=
-    case 2: if (constant == INT64_MIN) { r.lo = 1; r.hi = 0; } else r.hi = constant - 1; break;  // <
-    case 3: r.hi = constant; break;                                                   // <=
-    case 4: if (constant == INT64_MAX) { r.lo = 1; r.hi = 0; } else r.lo = constant + 1; break;  // >
-    case 5: r.lo = constant; break;                                                   // >=
-    default:                                                                          // c <= v < c2
-        r.lo = constant;
-        if (constant2 == INT64_MIN) { r.lo = 1; r.hi = 0; } else r.hi = constant2 - 1;
-        break;
-    }
-    return r;
 }
 
 hipError_t launch_masked_compare(const void* col, int type, const uint64_t* validity, const uint64_t* mask,

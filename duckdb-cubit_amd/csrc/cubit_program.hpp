@@ -1,0 +1,442 @@
+// The filter-program compiler, free of HIP so a CPU program can run it (tests/program_core.cpp): the
+// EvalProgram encoding the eval kernels decode, an integer comparison as a range, the walk of a pushed
+// filter tree, the expression algebra over bitvector leaves, the emitter that writes an expression as
+// a program and picks its form, and the postfix parser. What touches a table or the device: cubit_capi.hip.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <memory>
+#include <utility>
+#include <vector>
+
+#include "../../include/cubit_gpu.h"
+
+namespace cubit {
+
+constexpr int kMaxLeaves = 8;
+constexpr int kMaxOps = 16;  // 2 bits each in EvalProgram::ops
+// registers of the kernels' postfix stack: a program whose Emitter::max_depth exceeds it is not run
+constexpr int kMaxDepth = 4;
+
+enum : uint32_t { OP_AND = 1, OP_OR = 2, OP_ANDNOT = 3 };
+
+// A postfix program whose leaves appear in order 0..n_leaves-1: leaf k is pushed
+// (complemented if bit k of `negate`), then nops(k) binary ops are applied. The op counts
+// (4 bits per leaf) and opcodes (2 bits per op) are packed into words so the kernel decodes
+// them with scalar shifts (a runtime-indexed byte array in the kernel arguments compiles to
+// vector loads, each followed by an s_waitcnt vmcnt(0) that drains every outstanding load).
+// Evaluation forms: the general postfix interpreter, or a branch-free two-level form chosen
+// by the emitter (leaves ordered by group, gstart bit k = leaf k opens a group).
+enum : uint32_t { FORM_POSTFIX = 0, FORM_CONJ = 1, FORM_DNF = 2, FORM_CNF = 3 };
+
+struct EvalProgram {
+    const uint64_t* leaf[kMaxLeaves];
+    uint32_t negate;
+    uint32_t n_leaves;
+    uint32_t nops;    // 4 bits per leaf
+    uint32_t ops;     // 2 bits per op
+    uint32_t form;    // FORM_*; FORM_POSTFIX runs the postfix program (is_conjunction upgrades)
+    uint32_t gstart;  // FORM_DNF / FORM_CNF group starts
+};
+
+inline uint32_t prog_nops(const EvalProgram& p, int k) { return (p.nops >> (4 * k)) & 15u; }
+
+// A left-deep chain of ANDs (nops = 0,1,1,…; every op AND) evaluates as a plain conjunction.
+inline bool is_conjunction(const EvalProgram& p) {
+    if (p.n_leaves == 0 || prog_nops(p, 0) != 0) return false;
+    for (uint32_t k = 1; k < p.n_leaves; ++k)
+        if (prog_nops(p, (int)k) != 1 || ((p.ops >> (2 * (k - 1))) & 3u) != OP_AND) return false;
+    return true;
+}
+
+// the kernel template a program runs (dispatch_k_form, cubit_kernels.hip)
+inline uint32_t eval_form(const EvalProgram& p) {
+    if (p.form == FORM_DNF || p.form == FORM_CNF || p.form == FORM_CONJ) return p.form;
+    return is_conjunction(p) ? FORM_CONJ : FORM_POSTFIX;
+}
+
+// A comparison (CUBIT_CMP_* or the between form c <= v < c2) as the inclusive range [lo, hi] of
+// passing values, complemented when neg (!=); empty: lo > hi. clamp32 narrows it to INT32 values.
+struct CmpRange {
+    int64_t lo = INT64_MIN, hi = INT64_MAX;
+    int neg = 0;
+    bool empty() const { return lo > hi; }
+    bool contains(int64_t v) const { return (v >= lo && v <= hi) != (neg != 0); }
+    // the values both ranges hold (neither complemented)
+    CmpRange intersect(const CmpRange& o) const { return {std::max(lo, o.lo), std::min(hi, o.hi), 0}; }
+    void clamp32(int32_t& lo32, int32_t& hi32) const {
+        const bool none = lo > hi || lo > INT32_MAX || hi < INT32_MIN;
+        lo32 = none ? 1 : (int32_t)std::max<int64_t>(lo, INT32_MIN);
+        hi32 = none ? 0 : (int32_t)std::min<int64_t>(hi, INT32_MAX);
+    }
+};
+inline CmpRange cmp_range(int cmp, int64_t constant, int64_t constant2) {
+    CmpRange r;
+    switch (cmp) {
+    case 0: r.lo = r.hi = constant; break;                                            // =
+    case 1: r.lo = r.hi = constant; r.neg = 1; break;                                 // !=
+    case 2: if (constant == INT64_MIN) { r.lo = 1; r.hi = 0; } else r.hi = constant - 1; break;  // <
+    case 3: r.hi = constant; break;                                                   // <=
+    case 4: if (constant == INT64_MAX) { r.lo = 1; r.hi = 0; } else r.lo = constant + 1; break;  // >
+    case 5: r.lo = constant; break;                                                   // >=
+    default:                                                                          // c <= v < c2
+        r.lo = constant;
+        if (constant2 == INT64_MIN) { r.lo = 1; r.hi = 0; } else r.hi = constant2 - 1;
+        break;
+    }
+    return r;
+}
+
+// One past the last node of the subtree rooted at node i of a prefix-order node array, or -1 when
+// the array ends inside it. A negative child count reads as none.
+inline int filter_subtree_end(const cubit_filter_node* nodes, uint32_t n_nodes, uint32_t i) {
+    int64_t open = 1;  // subtrees begun and not yet walked
+    uint32_t j = i;
+    for (; open > 0; ++j) {
+        if (j >= n_nodes) return -1;
+        open += std::max<int32_t>(nodes[j].n_children, 0) - 1;
+    }
+    return (int)j;
+}
+
+// What a node may hold whatever the table: a kind in range, and cmp in 0…5 on a constant filter.
+enum class NodeCheck { kOk, kBadKind, kBadCmp };
+inline NodeCheck check_filter_node(const cubit_filter_node& f) {
+    if (f.kind < CUBIT_FILTER_CONSTANT || f.kind > CUBIT_FILTER_AND) return NodeCheck::kBadKind;
+    if (f.kind == CUBIT_FILTER_CONSTANT && (f.cmp < 0 || f.cmp > 5)) return NodeCheck::kBadCmp;
+    return NodeCheck::kOk;
+}
+
+// Expression over bitvectors. Leaves carry the row predicate they encode so that MVCC
+// update patches can recompute a row's bit from its visible value.
+struct Leaf {
+    const uint64_t* bv = nullptr;
+    int column = -1;  // -1: not derived from a column value (visibility, temp)
+    int pred = 0;     // 0 = cmp (v CMP c), 1 = valid (NN), 2 = bin (c <= v < constant2)
+    int cmp = 0;
+    int64_t constant = 0;
+    int64_t constant2 = 0;
+    // where its zone classes (zonemaps) come from: kZoneBits = bv is a table-owned index leaf or
+    // validity bitvector, classified from its own bits; kZoneStats = bv holds exactly the valid
+    // rows whose base value passes (cmp, constant) — a K0 or candidate-check leaf — classified
+    // from the column's per-zone min / max like a ConstantFilter's CheckStatistics; kZoneNone
+    // = visibility and materialised leaves (mixed everywhere)
+    int zsrc = 0;
+    // a leaf patched with MVCC updates keeps the classes of the base leaf it was copied from
+    // (zbv: that bitvector, for kZoneBits) except in the zones that hold an update record of
+    // column zdirty (there: mixed)
+    const uint64_t* zbv = nullptr;
+    int zdirty = -1;
+};
+enum { kZoneNone = 0, kZoneBits = 1, kZoneStats = 2 };
+
+struct Expr;
+using ExprP = std::shared_ptr<Expr>;
+struct Expr {
+    enum Kind { LEAF, AND, OR, ANDNOT, CONST_TRUE, CONST_FALSE } kind = CONST_FALSE;
+    Leaf leaf;
+    bool neg = false;  // LEAF only
+    ExprP a, b;
+};
+
+inline ExprP mk_node(Expr::Kind k) {
+    auto e = std::make_shared<Expr>();
+    e->kind = k;
+    return e;
+}
+inline ExprP mk_true() { return mk_node(Expr::CONST_TRUE); }
+inline ExprP mk_false() { return mk_node(Expr::CONST_FALSE); }
+inline ExprP mk_leaf(const Leaf& l, bool neg = false) {
+    auto e = mk_node(Expr::LEAF);
+    e->leaf = l;
+    e->neg = neg;
+    return e;
+}
+inline ExprP mk_not(const ExprP& x);
+inline ExprP mk_bin(Expr::Kind k, ExprP a, ExprP b) {
+    using K = Expr::Kind;
+    const bool at = a->kind == K::CONST_TRUE, af = a->kind == K::CONST_FALSE;
+    const bool bt = b->kind == K::CONST_TRUE, bf = b->kind == K::CONST_FALSE;
+    switch (k) {
+    case K::AND:
+        if (af || bf) return mk_false();
+        if (at) return b;
+        if (bt) return a;
+        break;
+    case K::OR:
+        if (at || bt) return mk_true();
+        if (af) return b;
+        if (bf) return a;
+        break;
+    case K::ANDNOT:
+        if (af || bt) return mk_false();
+        if (bf) return a;
+        if (at) return mk_not(b);
+        break;
+    default:
+        break;
+    }
+    auto e = mk_node(k);
+    e->a = std::move(a);
+    e->b = std::move(b);
+    return e;
+}
+// NOT pushed to the leaves (De Morgan); ANDNOT(a,b) = a & ~b → ~a | b
+inline ExprP mk_not(const ExprP& x) {
+    using K = Expr::Kind;
+    switch (x->kind) {
+    case K::CONST_TRUE: return mk_false();
+    case K::CONST_FALSE: return mk_true();
+    case K::LEAF: return mk_leaf(x->leaf, !x->neg);
+    case K::AND: return mk_bin(K::OR, mk_not(x->a), mk_not(x->b));
+    case K::OR: return mk_bin(K::AND, mk_not(x->a), mk_not(x->b));
+    case K::ANDNOT: return mk_bin(K::OR, mk_not(x->a), x->b);
+    }
+    return mk_false();
+}
+
+inline int count_leaves(const ExprP& e) {
+    if (e->kind == Expr::LEAF) return 1;
+    if (e->kind == Expr::CONST_TRUE || e->kind == Expr::CONST_FALSE) return 0;
+    return count_leaves(e->a) + count_leaves(e->b);
+}
+
+// registers the expression needs (Sethi–Ullman / Strahler number)
+inline int need(const ExprP& e) {
+    if (e->kind == Expr::LEAF) return 1;
+    const int l = need(e->a), r = need(e->b);
+    return l == r ? l + 1 : std::max(l, r);
+}
+
+// top-level conjuncts of e (a & ~leaf contributes the complemented leaf as a conjunct)
+inline void conj_parts(const ExprP& e, std::vector<ExprP>& out) {
+    if (e->kind == Expr::AND) {
+        conj_parts(e->a, out);
+        conj_parts(e->b, out);
+    } else if (e->kind == Expr::ANDNOT && e->b->kind == Expr::LEAF) {
+        conj_parts(e->a, out);
+        out.push_back(mk_leaf(e->b->leaf, !e->b->neg));
+    } else if (e->kind != Expr::CONST_TRUE) {
+        out.push_back(e);
+    }
+}
+inline void leaves_of(const ExprP& e, std::vector<const uint64_t*>& out) {
+    if (e->kind == Expr::LEAF) out.push_back(e->leaf.bv);
+    else if (e->a) {
+        leaves_of(e->a, out);
+        if (e->b) leaves_of(e->b, out);
+    }
+}
+
+// Emit postfix: the heavier child of an AND / OR first (Sethi–Ullman); a & ~b in that order (a heavier
+// b that is a leaf would go first, complemented, under an AND). ok: the program holds the expression;
+// max_depth: the stack it needs (fits checks both).
+struct Emitter {
+    EvalProgram prog{};
+    int n_ops = 0;
+    int depth = 0, max_depth = 0;
+    bool ok = true;
+    void leaf(const Leaf& l, bool neg) {
+        if (prog.n_leaves >= (uint32_t)kMaxLeaves) {
+            ok = false;
+            return;
+        }
+        const uint32_t k = prog.n_leaves++;
+        prog.leaf[k] = l.bv;
+        if (neg) prog.negate |= 1u << k;
+        max_depth = std::max(max_depth, ++depth);
+    }
+    void op(uint32_t o) {
+        const uint32_t k = prog.n_leaves - 1;
+        if (prog.n_leaves == 0 || n_ops >= kMaxOps || prog_nops(prog, (int)k) == 15) {
+            ok = false;
+            return;
+        }
+        prog.ops |= o << (2 * n_ops++);
+        prog.nops += 1u << (4 * k);
+        --depth;
+    }
+    // a conjunction of (possibly complemented) leaves: AND nodes, ANDNOT with a leaf on the right
+    static bool conj_leaves(const ExprP& e, std::vector<std::pair<Leaf, bool>>& out) {
+        switch (e->kind) {
+        case Expr::LEAF: out.push_back({e->leaf, e->neg}); return true;
+        case Expr::AND: return conj_leaves(e->a, out) && conj_leaves(e->b, out);
+        case Expr::ANDNOT:
+            if (e->b->kind != Expr::LEAF) return false;
+            if (!conj_leaves(e->a, out)) return false;
+            out.push_back({e->b->leaf, !e->b->neg});
+            return true;
+        default: return false;
+        }
+    }
+    using Lits = std::vector<std::pair<Leaf, bool>>;
+    static bool or_literals(const ExprP& e, Lits& out) {
+        if (e->kind == Expr::LEAF) {
+            out.push_back({e->leaf, e->neg});
+            return true;
+        }
+        if (e->kind == Expr::OR) return or_literals(e->a, out) && or_literals(e->b, out);
+        return false;
+    }
+    static void or_parts(const ExprP& e, std::vector<ExprP>& out) {
+        if (e->kind == Expr::OR) {
+            or_parts(e->a, out);
+            or_parts(e->b, out);
+        } else {
+            out.push_back(e);
+        }
+    }
+    // AND-ed parts; a & ~leaf contributes the complemented leaf as a part of its own
+    static bool and_parts(const ExprP& e, std::vector<Lits>& groups) {
+        if (e->kind == Expr::AND) return and_parts(e->a, groups) && and_parts(e->b, groups);
+        if (e->kind == Expr::ANDNOT) {
+            if (e->b->kind != Expr::LEAF) return false;
+            if (!and_parts(e->a, groups)) return false;
+            groups.push_back({{e->b->leaf, !e->b->neg}});
+            return true;
+        }
+        Lits g;
+        if (!or_literals(e, g)) return false;
+        groups.push_back(std::move(g));
+        return true;
+    }
+    // two-level program: groups of literals combined by `inner`, groups combined by `outer`;
+    // the postfix encoding of the same program is emitted alongside (interpreter fallback)
+    bool emit_groups(const std::vector<Lits>& groups, uint32_t inner, uint32_t outer, uint32_t form) {
+        size_t total = 0;
+        for (const auto& g : groups) total += g.size();
+        if (groups.empty() || total > (size_t)kMaxLeaves) return false;
+        uint32_t gstart = 0;
+        for (size_t gi = 0; gi < groups.size(); ++gi) {
+            gstart |= 1u << prog.n_leaves;
+            for (size_t i = 0; i < groups[gi].size(); ++i) {
+                leaf(groups[gi][i].first, groups[gi][i].second);
+                if (i) op(inner);
+            }
+            if (gi) op(outer);
+        }
+        prog.form = form;
+        prog.gstart = gstart;
+        return ok;
+    }
+    // top level: a pure conjunction is emitted as a left-deep AND chain (branch-free CONJ
+    // form, is_conjunction above); an OR of conjunctions (DNF) or an AND of ORs of literals
+    // (CNF) as a branch-free two-level program; anything else as postfix
+    void emit_top(const ExprP& e) {
+        Lits c;
+        if (e->kind != Expr::LEAF && conj_leaves(e, c)) {
+            leaf(c[0].first, c[0].second);
+            for (size_t i = 1; i < c.size(); ++i) {
+                leaf(c[i].first, c[i].second);
+                op(OP_AND);
+            }
+            return;
+        }
+        if (e->kind == Expr::OR) {
+            std::vector<ExprP> parts;
+            or_parts(e, parts);
+            std::vector<Lits> groups;
+            bool dnf = true;
+            for (const auto& p : parts) {
+                Lits g;
+                if (!conj_leaves(p, g)) {
+                    dnf = false;
+                    break;
+                }
+                groups.push_back(std::move(g));
+            }
+            if (dnf) {
+                Emitter trial;
+                if (trial.emit_groups(groups, OP_AND, OP_OR, FORM_DNF)) {
+                    *this = trial;
+                    return;
+                }
+            }
+        }
+        if (e->kind == Expr::AND || e->kind == Expr::ANDNOT) {
+            std::vector<Lits> groups;
+            if (and_parts(e, groups)) {
+                Emitter trial;
+                if (trial.emit_groups(groups, OP_OR, OP_AND, FORM_CNF)) {
+                    *this = trial;
+                    return;
+                }
+            }
+        }
+        emit(e);
+    }
+    void emit(const ExprP& e) {
+        switch (e->kind) {
+        case Expr::LEAF: leaf(e->leaf, e->neg); return;
+        case Expr::AND:
+        case Expr::OR: {
+            const uint32_t o = e->kind == Expr::AND ? OP_AND : OP_OR;
+            if (need(e->b) > need(e->a)) {
+                emit(e->b);
+                emit(e->a);
+            } else {
+                emit(e->a);
+                emit(e->b);
+            }
+            op(o);
+            return;
+        }
+        case Expr::ANDNOT: {
+            if (need(e->b) > need(e->a) && e->b->kind == Expr::LEAF) {
+                // a & ~b == (~b) & a with b a leaf: emit complemented leaf first
+                leaf(e->b->leaf, !e->b->neg);
+                emit(e->a);
+                op(OP_AND);
+            } else {
+                emit(e->a);
+                emit(e->b);
+                op(OP_ANDNOT);
+            }
+            return;
+        }
+        default: ok = false; return;
+        }
+    }
+};
+
+// one kernel pass evaluates e: its program holds it and the kernels' stack is deep enough
+inline bool fits(const ExprP& e) {
+    Emitter em;
+    em.emit_top(e);
+    return em.ok && em.max_depth <= kMaxDepth;
+}
+
+// A caller's postfix program (cubit_bitvector_eval: an entry >= 0 pushes that leaf, a CUBIT_OP_*
+// pops two values and pushes one) as an expression, or the first check it fails.
+struct PostfixParse {
+    enum Error { kNone, kLeafRange, kUnderflow, kBadOpcode, kEmpty, kLeftOver } error;
+    ExprP expr;     // kNone
+    uint32_t at;    // kLeafRange, kUnderflow, kBadOpcode: the failing entry's index …
+    int32_t value;  // … and the entry
+    size_t left;    // kEmpty, kLeftOver: the values the program leaves on the stack
+};
+inline PostfixParse parse_postfix(const uint64_t* const* leaves, uint32_t n_leaves, uint32_t leaf_negate,
+                                  const int32_t* prog, uint32_t n_prog) {
+    using P = PostfixParse;
+    std::vector<ExprP> st;
+    for (uint32_t i = 0; i < n_prog; ++i) {
+        const int32_t x = prog[i];
+        if (x >= 0) {
+            if ((uint32_t)x >= n_leaves) return {P::kLeafRange, nullptr, i, x, 0};
+            Leaf l;
+            l.bv = leaves[x];
+            st.push_back(mk_leaf(l, x < 32 && ((leaf_negate >> x) & 1u) != 0));
+        } else {
+            if (st.size() < 2) return {P::kUnderflow, nullptr, i, x, 0};
+            if (x != CUBIT_OP_AND && x != CUBIT_OP_OR && x != CUBIT_OP_ANDNOT) return {P::kBadOpcode, nullptr, i, x, 0};
+            const ExprP b = st.back(), a = st[st.size() - 2];
+            st.resize(st.size() - 2);
+            st.push_back(mk_bin(x == CUBIT_OP_AND ? Expr::AND : x == CUBIT_OP_OR ? Expr::OR : Expr::ANDNOT, a, b));
+        }
+    }
+    if (st.size() != 1) return {st.empty() ? P::kEmpty : P::kLeftOver, nullptr, 0, 0, st.size()};
+    return {P::kNone, st[0], 0, 0, 0};
+}
+
+}  // namespace cubit
