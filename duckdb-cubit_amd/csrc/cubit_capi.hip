@@ -688,6 +688,47 @@ int cubit_build_bitvector(cubit_ctx* ctx, const void* d_col, int type, const uin
     return CUBIT_OK;
 }
 
+int cubit_bitslice_build(cubit_ctx* ctx, const void* d_col, int type, const uint64_t* d_validity, uint64_t n_rows,
+                         int64_t base, uint32_t n_slices, uint64_t* const* d_slices) {
+    if (!ctx || !d_col || (n_slices && !d_slices)) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(ctx);
+    if (type != CUBIT_TYPE_INT32 && type != CUBIT_TYPE_INT64 && !type_is_keyed(type))
+        return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
+    if (n_slices > kMaxSlices) return fail(CUBIT_ERR_INVALID, "%u slices (0 … 64)", n_slices);
+    SliceSet out{};
+    for (uint32_t s = 0; s < n_slices; ++s) {
+        if (!d_slices[s]) return fail(CUBIT_ERR_INVALID, "slice %u is null", s);
+        out.s[s] = d_slices[s];
+    }
+    hipEvent_t e0, e1;
+    if (int rc = timing_events(ctx, e0, e1)) return rc;
+    HIP_CHECK(launch_bitslice_build(d_col, type, d_validity, n_rows, base, n_slices, out, ctx->stream, e0, e1));
+    if (n_slices == 0 && e0) {  // nothing launched: the timed slot still reads as a (zero) launch
+        HIP_CHECK(hipEventRecord(e0, ctx->stream));
+        HIP_CHECK(hipEventRecord(e1, ctx->stream));
+    }
+    return CUBIT_OK;
+}
+
+int cubit_bitslice_compare(cubit_ctx* ctx, const uint64_t* const* d_slices, uint32_t n_slices,
+                           const uint64_t* d_validity, uint64_t n_rows, uint64_t lo, uint64_t hi, int negate,
+                           uint64_t* d_words) {
+    if (!ctx || !d_words || (n_slices && !d_slices)) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(ctx);
+    if (n_slices > kMaxSlices) return fail(CUBIT_ERR_INVALID, "%u slices (0 … 64)", n_slices);
+    auto aligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    if (!aligned(d_words) || !aligned(d_validity)) return fail(CUBIT_ERR_INVALID, "bitvectors must be 16-byte aligned");
+    SliceSet sl{};
+    for (uint32_t s = 0; s < n_slices; ++s) {
+        if (!d_slices[s] || !aligned(d_slices[s])) return fail(CUBIT_ERR_INVALID, "slice %u is null or unaligned", s);
+        sl.s[s] = const_cast<uint64_t*>(d_slices[s]);
+    }
+    hipEvent_t e0, e1;
+    if (int rc = timing_events(ctx, e0, e1)) return rc;
+    HIP_CHECK(launch_bitslice_compare(sl, n_slices, d_validity, n_rows, lo, hi, negate, d_words, ctx->stream, e0, e1));
+    return CUBIT_OK;
+}
+
 }  // extern "C"
 
 extern "C" int cubit_bitvector_eval(cubit_ctx* ctx, const uint64_t* const* d_leaves, uint32_t n_leaves,
@@ -913,6 +954,9 @@ struct cubit_table {
     std::map<int, Column> cols;
     std::map<int, Index> idx;
     std::map<int, Index> bins;  // CUBIT_INDEX_BINS (secondary)
+    // CUBIT_INDEX_SLICED (secondary): bvs = the slices of key - vmin, least significant first (as
+    // many as the bit length of vmax - vmin), keys empty
+    std::map<int, Index> sliced;
     // MVCC delta
     std::unique_ptr<DevBuf> del_rows, del_ids;
     uint64_t n_del = 0;
@@ -982,6 +1026,8 @@ struct cubit_table {
     uint32_t last_live = 0, last_zones = 0;  // zones the last scan evaluated / the partition has
     bool use_packed = false;  // cubit_table_use_packed_filter (off by default: slower than K0)
     uint32_t last_packed = 0;  // leaves the last plan built straight from packed segments
+    bool use_sliced = true;  // cubit_table_use_sliced
+    uint32_t last_sliced = 0;  // leaves the last plan built from a bit-sliced index
     bool use_narrowing = true;  // cubit_table_use_narrowing
     uint32_t last_narrowed = 0;  // K0 leaves the last plan built only at the rows a mask kept
     std::vector<int32_t> last_narrow_cols;  // columns of the last plan's K0 leaves, in build order
@@ -1083,6 +1129,7 @@ int install_column(cubit_table* t, int col, Column&& c) {
     drop_patches(t, col);
     t->idx.erase(col);
     t->bins.erase(col);
+    t->sliced.erase(col);
     return CUBIT_OK;
 }
 
@@ -1715,6 +1762,63 @@ int build_index_bitvectors(cubit_table* t, int col, const Column& c, Index&& ix)
     return CUBIT_OK;
 }
 
+// ---- bit-sliced index (CUBIT_INDEX_SLICED): bvs = the slices of key - vmin
+
+SliceSet slice_set(const Index& ix) {
+    SliceSet s{};
+    for (size_t k = 0; k < ix.bvs.size() && k < kMaxSlices; ++k) s.s[k] = ix.bvs[k];
+    return s;
+}
+
+// all-zero high slices until the index holds n of them (rows already sliced have 0 there)
+int sliced_grow(cubit_table* t, Index& ix, uint32_t n) {
+    while (ix.bvs.size() < n) {
+        auto b = std::make_unique<DevBuf>();
+        if (int rc = alloc_table_bv(t, *b)) return fail(rc, "slice allocation failed after %zu of %u", ix.bvs.size(), n);
+        ix.bvs.push_back(static_cast<uint64_t*>(b->p));
+        ix.owned.push_back(std::move(b));
+    }
+    ix.bytes = ix.owned.size() * t->cap_words * 8;
+    return CUBIT_OK;
+}
+
+// The slices of a column as it stands (n_rows rows), base = its smallest valid key: one build.
+// `into` keeps its bitvectors where their count allows (a rebuild after maintenance).
+int build_sliced(cubit_table* t, const Column& c, uint64_t n_rows, Index& into) {
+    Index& ix = into;
+    ix.encoding = CUBIT_INDEX_SLICED;
+    ix.exact_all = false;
+    ix.keys.clear();
+    bool any = false;
+    if (n_rows) {
+        std::vector<int64_t> distinct;
+        if (int rc = value_stats(t, c.data, ktype(c), c.validity, n_rows, distinct, false, ix.vmin, ix.vmax, any)) return rc;
+    }
+    ix.empty = !any;
+    const uint32_t bits = any ? sliced_bits(ix.vmin, ix.vmax) : 0;
+    if (ix.bvs.size() > bits) {  // a narrower span: the high slices go
+        ix.bvs.resize(bits);
+        ix.owned.resize(bits);
+    }
+    if (int rc = sliced_grow(t, ix, bits)) return rc;
+    if (bits) {
+        hipEvent_t e0, e1;
+        if (int rc = timing_events(t->ctx, e0, e1)) return rc;
+        HIP_CHECK(launch_bitslice_build(c.data, ktype(c), c.validity, n_rows, ix.vmin, bits, slice_set(ix), t->ctx->stream,
+                                        e0, e1));
+    }
+    HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+    return CUBIT_OK;
+}
+
+// Take the slices instead of K0's pass over the column when they move fewer bytes: the compare
+// reads b slices and the validity and writes one bitvector, (b + 2)/8 bytes per row, where K0 reads
+// the column's element. From traffic alone (b < 30 on a 4-byte column, b < 62 on an 8-byte one), and
+// the measurement agrees: both kernels stream at the same rate, 12 and 24 slices take 0.40 of K0's
+// time at 612 M rows and 64 slices of an 8-byte column tie with it (DESIGN.md §3,
+// scripts/sliced_timing.py).
+bool sliced_moves_fewer_bytes(uint32_t bits, uint64_t elem_bytes) { return bits + 2 < 8 * elem_bytes; }
+
 // CUBIT_QUANTILE_PLAIN_ADDS: the histogram passes without the wave-level pre-aggregation
 // (diagnostic; scripts/quantile_timing.py times both forms)
 bool quantile_wave_agg() {
@@ -1801,12 +1905,21 @@ extern "C" int cubit_table_build_index(cubit_table* t, int col, int encoding, co
     CUBIT_LOCK(t->ctx);
     auto it = t->cols.find(col);
     if (it == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column %d not registered", col);
-    if (encoding != CUBIT_INDEX_RANGE && encoding != CUBIT_INDEX_EQUALITY && encoding != CUBIT_INDEX_BINS)
+    if (encoding != CUBIT_INDEX_RANGE && encoding != CUBIT_INDEX_EQUALITY && encoding != CUBIT_INDEX_BINS &&
+        encoding != CUBIT_INDEX_SLICED)
         return fail(CUBIT_ERR_INVALID, "encoding %d", encoding);
     if (encoding == CUBIT_INDEX_BINS && (n < 2 || !values)) return fail(CUBIT_ERR_INVALID, "bins need >= 2 edges");
+    if (encoding == CUBIT_INDEX_SLICED && n) return fail(CUBIT_ERR_INVALID, "a bit-sliced index takes no keys");
     if (n && !values) return fail(CUBIT_ERR_INVALID, "values is null");
     if (int rc = set_device(t->ctx)) return rc;
     const Column& c = it->second;
+    if (encoding == CUBIT_INDEX_SLICED) {  // an empty partition or no valid row: an empty index, no slices
+        Index ix;
+        if (int rc = build_sliced(t, c, t->n_rows, ix)) return rc;
+        drop_patches(t, col);
+        t->sliced[col] = std::move(ix);
+        return CUBIT_OK;
+    }
     // a FLOAT / DOUBLE column's keys are given as bit patterns and held as their comparison keys
     // (-0.0 and +0.0, or two NaNs, become one key)
     std::vector<int64_t> keyed;
@@ -1915,7 +2028,7 @@ extern "C" int cubit_table_index_info(cubit_table* t, int col, uint32_t* n_bitve
     CUBIT_LOCK(t->ctx);
     uint32_t nb = 0;
     uint64_t by = 0;
-    for (auto* m : {&t->idx, &t->bins}) {
+    for (auto* m : {&t->idx, &t->bins, &t->sliced}) {
         auto it = m->find(col);
         if (it != m->end()) {
             nb += (uint32_t)it->second.bvs.size();
@@ -1967,6 +2080,9 @@ extern "C" int cubit_table_save_index(cubit_table* t, int col, int encoding, con
     if (encoding == CUBIT_INDEX_BINS) {
         auto it = t->bins.find(col);
         if (it != t->bins.end()) ix = &it->second;
+    } else if (encoding == CUBIT_INDEX_SLICED) {
+        auto it = t->sliced.find(col);
+        if (it != t->sliced.end()) ix = &it->second;
     } else {
         auto it = t->idx.find(col);
         if (it != t->idx.end() && it->second.encoding == encoding) ix = &it->second;
@@ -2035,9 +2151,13 @@ extern "C" int cubit_table_load_index(cubit_table* t, int col, const char* path)
         return bad("a version-1 index file holds raw-value keys, this column's type needs comparison keys");
     }
     if (h.n_rows != t->n_rows || h.nwp != t->nwp) return bad("index was built for a partition of another size");
-    if (h.encoding > CUBIT_INDEX_BINS) return bad("unknown encoding");
-    const uint64_t want_bv = h.encoding == CUBIT_INDEX_BINS ? (h.n_keys ? h.n_keys - 1 : 0) : h.n_keys;
-    if (h.n_bv != want_bv || h.n_keys > (1ull << 32)) return bad("inconsistent header");
+    if (h.encoding > CUBIT_INDEX_SLICED) return bad("unknown encoding");
+    // a bit-sliced index holds no keys and one slice per bit of vmax - vmin (none without a valid row)
+    const uint64_t want_bv = h.encoding == CUBIT_INDEX_SLICED ? (h.empty ? 0 : sliced_bits(h.vmin, h.vmax))
+                             : h.encoding == CUBIT_INDEX_BINS ? (h.n_keys ? h.n_keys - 1 : 0)
+                                                              : h.n_keys;
+    if (h.n_bv != want_bv || h.n_keys > (1ull << 32) || (h.encoding == CUBIT_INDEX_SLICED && h.n_keys))
+        return bad("inconsistent header");
     Index ix;
     ix.encoding = (int)h.encoding;
     ix.exact_all = h.exact_all != 0;
@@ -2068,6 +2188,7 @@ extern "C" int cubit_table_load_index(cubit_table* t, int col, const char* path)
     std::fclose(f);
     drop_patches(t, col);
     if (ix.encoding == CUBIT_INDEX_BINS) t->bins[col] = std::move(ix);
+    else if (ix.encoding == CUBIT_INDEX_SLICED) t->sliced[col] = std::move(ix);
     else t->idx[col] = std::move(ix);
     return CUBIT_OK;
 }
@@ -2271,7 +2392,7 @@ int grow_bitvectors(cubit_table* t, uint64_t words) {
         p = np;
         return CUBIT_OK;
     };
-    for (auto* m : {&t->idx, &t->bins}) {
+    for (auto* m : {&t->idx, &t->bins, &t->sliced}) {
         for (auto& kv : *m) {
             Index& ix = kv.second;
             for (size_t k = 0; k < ix.owned.size(); ++k) {
@@ -2498,7 +2619,8 @@ extern "C" int cubit_table_append(cubit_table* t, uint64_t n_new, const int* col
                                          n_old, n_new, s));
         }
         Index* ixs[2] = {t->idx.count(col) ? &t->idx[col] : nullptr, t->bins.count(col) ? &t->bins[col] : nullptr};
-        if (!ixs[0] && !ixs[1]) continue;
+        Index* sx = t->sliced.count(col) ? &t->sliced[col] : nullptr;
+        if (!ixs[0] && !ixs[1] && !sx) continue;
         // statistics of the appended slice (+ its distinct values for an every-distinct-value index)
         bool want_distinct = ixs[0] && ixs[0]->exact_all;
         std::vector<int64_t> added;
@@ -2549,6 +2671,29 @@ extern "C" int cubit_table_append(cubit_table* t, uint64_t n_new, const int* col
                 t->n_rows = n_old;
                 t->nwp = padded_words(n_old);
                 if (rc) return rc;
+            }
+        }
+        // the bit-sliced index (NULL appended rows are 0 in every slice, as the padding they replace)
+        if (sx && sany) {
+            if (sx->empty || smin < sx->vmin) {
+                // the first valid rows, or a key below the base: every offset changes, so the slices
+                // are rebuilt in one build from the whole column, which holds the appended rows already
+                if (int rc2 = build_sliced(t, c, n_total, *sx)) return rc2;
+            } else {
+                // a key above the top first adds all-zero high slices (the old rows have 0 there); then
+                // the appended rows are sliced alone and every slice spliced at bit n_old
+                const int64_t top = std::max(sx->vmax, smax);
+                const uint32_t bits = sliced_bits(sx->vmin, top);
+                DevBuf tmp_sl;
+                if (bits && hipMalloc(&tmp_sl.p, slice_words * 8 * bits) != hipSuccess)
+                    return fail(CUBIT_ERR_OOM, "append staging allocation failed");
+                if (int rc2 = sliced_grow(t, *sx, bits)) return rc2;
+                sx->vmax = top;
+                SliceSet fresh{};
+                for (uint32_t k = 0; k < bits; ++k) fresh.s[k] = static_cast<uint64_t*>(tmp_sl.p) + (uint64_t)k * slice_words;
+                HIP_CHECK(launch_bitslice_build(tmp_col.p, ktype(c), slice_valid, n_new, sx->vmin, bits, fresh, s));
+                for (uint32_t k = 0; k < bits; ++k) HIP_CHECK(launch_splice_bits(sx->bvs[k], fresh.s[k], n_old, n_new, s));
+                HIP_CHECK(hipStreamSynchronize(s));  // tmp_sl goes out of scope
             }
         }
         HIP_CHECK(hipStreamSynchronize(s));  // tmp_col / tmp_valid reused by the next column
@@ -2622,6 +2767,25 @@ int apply_records(cubit_table* t, int col, Column& c, const int64_t* rows_p, con
         ix->vmax = was_empty ? added.back() : std::max(ix->vmax, added.back());
         ix->empty = false;
         if (int rc = maintain_exact_keys(t, col, *ix, added, old_min, was_empty)) return rc;
+    }
+    // the bit-sliced index, from the column as the merge left it: the words holding a merged row are
+    // sliced again (a merged NULL clears its row in every slice, NULL → value sets it); a value above
+    // the top first adds all-zero high slices; one below the base (or the first valid rows) moves
+    // every offset, so the slices are rebuilt in one build
+    auto sit = t->sliced.find(col);
+    if (sit != t->sliced.end()) {
+        Index& sx = sit->second;
+        if (!added.empty() && (sx.empty || added.front() < sx.vmin)) {
+            if (int rc = build_sliced(t, c, t->n_rows, sx)) return rc;
+        } else if (!sx.empty) {
+            if (!added.empty() && added.back() > sx.vmax) {
+                if (int rc = sliced_grow(t, sx, sliced_bits(sx.vmin, added.back()))) return rc;
+                sx.vmax = added.back();
+            }
+            HIP_CHECK(launch_bitslice_reslice(rows_p, m, c.data, ktype(c), c.validity, t->n_rows, sx.vmin,
+                                              (uint32_t)sx.bvs.size(), slice_set(sx), s));
+            HIP_CHECK(hipStreamSynchronize(s));
+        }
     }
     return CUBIT_OK;
 }
@@ -2898,18 +3062,46 @@ IndexView view_of(const cubit_table* t, int col, const Index& ix) {
 }
 
 // A K0 leaf whose bitvector is not built yet: {valid rows: v cmp c} of column col into bv.
+// cmp = kCmpBetween: the interval c <= v < c2 (a Leaf of pred 2).
 struct PendingK0 {
     uint64_t* bv;
     int col, cmp;
     int64_t c;
+    int64_t c2 = 0;
 };
 
-// Build a K0 leaf over the whole column (from the BITPACKING segments when enabled).
+// the column's bit-sliced index when a whole-column comparison should be answered from it
+const Index* sliced_for_k0(const cubit_table* t, int col) {
+    if (!t->use_sliced) return nullptr;
+    auto it = t->sliced.find(col);
+    if (it == t->sliced.end() || it->second.empty) return nullptr;
+    const Column& cl = t->cols.at(col);
+    return sliced_moves_fewer_bytes((uint32_t)it->second.bvs.size(), type_is32(cl.type) ? 4 : 8) ? &it->second : nullptr;
+}
+
+// Build a K0 leaf over the whole column (from the column's slices where they move fewer bytes, or
+// from the BITPACKING segments when enabled).
 int compute_k0(cubit_table* t, const PendingK0& k) {
     const Column& cl = t->cols.at(k.col);
     hipError_t e;
+    if (const Index* sx = sliced_for_k0(t, k.col)) {
+        // bit for bit the leaf K0 builds: the valid rows whose base key passes. An interval that
+        // misses or covers the slices' range is built all the same (all zero / the valid rows), so
+        // the leaf keeps its predicate for the patches of visible updates.
+        const uint32_t bits = (uint32_t)sx->bvs.size();
+        const SlicedInterval si = sliced_interval(k.cmp, k.c, k.c2, sx->vmin, bits);
+        const uint64_t max = bits >= 64 ? ~0ull : (1ull << bits) - 1;
+        const bool iv = si.kind == SlicedInterval::kInterval;
+        hipEvent_t e0, e1;
+        if (int rc = timing_events(t->ctx, e0, e1)) return rc;
+        e = launch_bitslice_compare(slice_set(*sx), bits, cl.validity, t->n_rows, iv ? si.lo : 0, iv ? si.hi : max,
+                                    iv ? si.negate : si.kind == SlicedInterval::kFalse, k.bv, t->ctx->stream, e0, e1);
+        t->last_sliced++;
+        if (e != hipSuccess) return fail(CUBIT_ERR_HIP, "bit-slice compare kernel: %s", hipGetErrorString(e));
+        return CUBIT_OK;
+    }
     // (UBIGINT segments: the packed compare orders values as signed; such columns compare unpacked)
-    if (cl.bp_n_groups && t->use_packed && cl.type != CUBIT_TYPE_UINT64) {
+    if (cl.bp_n_groups && t->use_packed && cl.type != CUBIT_TYPE_UINT64 && k.cmp != kCmpBetween) {
         // straight from the BITPACKING segments: w/8 bytes per row instead of sizeof(T)
         e = hipMemsetAsync(k.bv, 0, t->nwp * 8, t->ctx->stream);
         if (e == hipSuccess)
@@ -2918,7 +3110,7 @@ int compute_k0(cubit_table* t, const PendingK0& k) {
                                          cl.validity, k.cmp, k.c, 0, k.bv, t->ctx->stream, cl.bp_simple_width);
         t->last_packed++;
     } else {
-        e = launch_compare_bitvector(cl.data, ktype(cl), cl.validity, t->n_rows, k.cmp, k.c, k.bv, t->ctx->stream);
+        e = launch_compare_bitvector(cl.data, ktype(cl), cl.validity, t->n_rows, k.cmp, k.c, k.bv, t->ctx->stream, k.c2);
     }
     if (e != hipSuccess) return fail(CUBIT_ERR_HIP, "compare kernel: %s", hipGetErrorString(e));
     return CUBIT_OK;
@@ -2964,18 +3156,53 @@ struct Planner {
     // deferred (pending) until the plan is complete: inside a conjunction it may be narrowed to
     // the rows the other filters keep (narrow_k0), as the reference's filter loop does.
     std::vector<PendingK0> pending;
-    ExprP raw_compare(int col, int cmp, int64_t c) {
+    // cmp = kCmpBetween: the interval c <= v < c2 as one leaf of pred 2 (plan_and, sliced columns).
+    // A column with a bit-sliced index folds a comparison that no key of the slices' range passes,
+    // or every one does, into FALSE / the valid rows without a launch — only when it also folds
+    // against the range widened by the column's update records (the rule view_of applies to the
+    // other encodings); inside the widened range the leaf is built and keeps its predicate.
+    ExprP raw_compare(int col, int cmp, int64_t c, int64_t c2 = 0) {
+        if (const Index* sx = sliced_for_k0(t, col)) {
+            const SlicedInterval si = sliced_interval(cmp, c, c2, sx->vmin, (uint32_t)sx->bvs.size());
+            if (si.kind != SlicedInterval::kInterval) {
+                int64_t wmin = sx->vmin, wmax = sx->vmax;
+                auto uit = t->upd.find(col);
+                if (uit != t->upd.end() && !uit->second.stat_values.empty()) {
+                    wmin = std::min(wmin, uit->second.stat_values.front());
+                    wmax = std::max(wmax, uit->second.stat_values.back());
+                }
+                if (sliced_interval(cmp, c, c2, wmin, sliced_bits(wmin, wmax)).kind == si.kind)
+                    return si.kind == SlicedInterval::kFalse ? mk_false() : nn(col);
+            }
+        }
         uint64_t* bv = nullptr;
         if ((rc = scratch_bv(t, &bv))) return nullptr;
-        pending.push_back({bv, col, cmp, c});
+        pending.push_back({bv, col, cmp, c, c2});
         Leaf l;
         l.bv = bv;
         l.column = col;
-        l.cmp = cmp;
+        if (cmp == kCmpBetween) {
+            l.pred = 2;
+            l.constant2 = c2;
+        } else {
+            l.cmp = cmp;
+        }
         l.constant = c;
         l.zsrc = kZoneStats;
         return mk_leaf(l);
     }
+
+    // lo <= v <= hi (folded constant filters, not empty) on a column whose only index is bit-sliced:
+    // one leaf, so `a <= x AND x < b` is one pass over the slices, not two
+    ExprP sliced_range(int col, const CmpRange& r) {
+        const bool has_lo = r.lo != INT64_MIN, has_hi = r.hi != INT64_MAX;
+        if (!has_lo && !has_hi) return nn(col);
+        if (!has_hi) return raw_compare(col, CUBIT_CMP_GE, r.lo);
+        if (!has_lo) return raw_compare(col, CUBIT_CMP_LE, r.hi);
+        if (r.lo == r.hi) return raw_compare(col, CUBIT_CMP_EQ, r.lo);
+        return raw_compare(col, kCmpBetween, r.lo, r.hi + 1);
+    }
+    bool sliced_only(int col) const { return t->sliced.count(col) && !t->idx.count(col) && !t->bins.count(col); }
 
     // {v < c} from a range index; nullptr when the index cannot answer exactly
     ExprP range_lt(int col, const IndexView& ix, int64_t c) {
@@ -3204,7 +3431,9 @@ struct Planner {
             kids.push_back(j);
             const cubit_filter_node& c = nodes[j];
             if (c.kind == CUBIT_FILTER_CONSTANT && c.n_children == 0 && c.cmp != CUBIT_CMP_NE && c.cmp >= 0 &&
-                c.cmp <= 5 && (t->bins.count(c.column) || exact_equality(c.column))) {
+                c.cmp <= 5 &&
+                (t->bins.count(c.column) || exact_equality(c.column) ||
+                 (sliced_only(c.column) && sliced_for_k0(t, c.column)))) {
                 Bounds& bd = by_col[c.column];
                 bd.r = bd.r.intersect(cmp_range(c.cmp, c.constant, 0));
                 bd.members.push_back(j);
@@ -3218,6 +3447,7 @@ struct Planner {
             const HalfOpen h(bd.r);
             if (bd.r.empty()) e = mk_false();
             else if (t->bins.count(col)) e = interval_from_bins(col, h.lo, h.hi, h.has_lo, h.has_hi);
+            else if (bd.members.size() > 1 && sliced_only(col)) e = sliced_range(col, bd.r);
             if (!e && !rc && bd.members.size() > 1) {
                 // two or more bounds on an every-value equality index: one union for the interval
                 if (const Index* eq = exact_equality(col)) {
@@ -3343,7 +3573,8 @@ int narrow_k0(cubit_table* t, ExprP& e, std::vector<PendingK0>& pending, bool al
     std::vector<const uint64_t*> narrow_bvs;
     Emitter::Lits rest;
     for (const auto& lit : lits) {
-        if (!lit.second && is_pending(lit.first.bv) &&
+        // (an interval leaf, pred 2, is built in full: the masked compare takes one comparison)
+        if (!lit.second && lit.first.pred != 2 && is_pending(lit.first.bv) &&
             std::find(narrow_bvs.begin(), narrow_bvs.end(), lit.first.bv) == narrow_bvs.end())
             narrow_bvs.push_back(lit.first.bv);
         else
@@ -3685,6 +3916,9 @@ const ZoneMap& stats_zone_map(cubit_table* t, const Leaf& l) {
         if (!(cz.fl[z] & 1)) {
             none = true;
             all = false;
+        } else if (l.pred == 2) {  // c <= v < constant2
+            none = hi < c || lo >= l.constant2;
+            all = lo >= c && hi < l.constant2 && (cz.fl[z] & 2);
         } else {
             switch (l.cmp) {
             case CUBIT_CMP_EQ: none = c < lo || c > hi; all = lo == c && hi == c; break;
@@ -4101,6 +4335,7 @@ int plan_program(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_node
     t->scratch_used = 0;
     t->last_passes = 0;
     t->last_packed = 0;
+    t->last_sliced = 0;
     t->last_narrowed = 0;
     t->last_narrow_cols.clear();
     ExprP e;
@@ -4577,6 +4812,20 @@ extern "C" int cubit_table_last_narrowed(cubit_table* t, uint32_t* n_leaves) {
     if (!t || !n_leaves) return fail(CUBIT_ERR_INVALID, "null argument");
     CUBIT_LOCK(t->ctx);
     *n_leaves = t->last_narrowed;
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_use_sliced(cubit_table* t, int on) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    t->use_sliced = on != 0;
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_last_sliced(cubit_table* t, uint32_t* n_leaves) {
+    if (!t || !n_leaves) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    *n_leaves = t->last_sliced;
     return CUBIT_OK;
 }
 

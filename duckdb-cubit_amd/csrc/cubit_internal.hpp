@@ -177,6 +177,27 @@ struct MultiKeyArgs {
 };
 hipError_t launch_compare_bitvectors(const void* col, int type, const uint64_t* validity, uint64_t n_rows, int cmp,
                                      const MultiKeyArgs& a, hipStream_t stream);
+// Bit-sliced index (CUBIT_INDEX_SLICED): slice s holds bit s of u = (uint64)key - (uint64)base of
+// every valid row (NULL rows and padding 0); each slice is padded_words(n_rows) words.
+constexpr uint32_t kMaxSlices = 64;
+struct SliceSet {
+    uint64_t* s[kMaxSlices];  // least significant first
+};
+// the column → its n_slices slices, one pass of the column per kMultiKeys slices (every word of
+// every slice written). ev0 / ev1 (optional) are stamped by the first / last dispatch.
+hipError_t launch_bitslice_build(const void* col, int type, const uint64_t* validity, uint64_t n_rows, int64_t base,
+                                 uint32_t n_slices, const SliceSet& out, hipStream_t stream, hipEvent_t ev0 = nullptr,
+                                 hipEvent_t ev1 = nullptr);
+// out = valid ∧ (lo <= u <= hi), complemented under valid when negate; validity null = every row
+// below n_rows (read only below ceil(n_rows / 64) words; 16-byte aligned, as are the slices and out)
+hipError_t launch_bitslice_compare(const SliceSet& slices, uint32_t n_slices, const uint64_t* validity, uint64_t n_rows,
+                                   uint64_t lo, uint64_t hi, int negate, uint64_t* out, hipStream_t stream,
+                                   hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// after a merge: every 64-row word holding one of the m merged rows (ascending) sliced again from
+// the column as it stands
+hipError_t launch_bitslice_reslice(const int64_t* rows, uint64_t m, const void* col, int type, const uint64_t* validity,
+                                   uint64_t n_rows, int64_t base, uint32_t n_slices, const SliceSet& slices,
+                                   hipStream_t stream);
 // index-build statistics (out3 = {min, max, valid count}, pre-set by the caller) and the
 // presence bitmap of the valid values (bit v - vmin, `range` bits, zeroed by the caller)
 hipError_t launch_column_minmax(const void* col, int type, const uint64_t* validity, uint64_t n_rows, int64_t* out3,

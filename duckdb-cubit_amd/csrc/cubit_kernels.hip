@@ -2012,6 +2012,181 @@ hipError_t launch_compare_m(const void* col, int type, const uint64_t* validity,
                                                        stream);
 }
 
+// ------------------------------------------------------------------ bit-sliced index
+//
+// A bit-sliced index (O'Neil & Quass 1997; Rinfret, O'Neil & O'Neil 2001) holds one bitvector per
+// bit of u = (uint64)key - (uint64)base: bit r of slice s = valid(r) && ((u_r >> s) & 1). Any
+// comparison with a constant is then a ripple of AND / OR / ANDNOT over 64-row words from the top
+// slice down: no unpack, no per-row compare, b/8 bytes read per row for a b-bit span.
+
+// Build: bitslice_build_kernel follows compare_bitvectors_kernel — a wave takes 64 words, 16 words'
+// values are loaded ahead, each (word, slice) is one ballot kept by lane j for word j, and every
+// slice's 64 words leave as one 512-byte store. A pass makes at most kMultiKeys slices (the bits
+// s0 … s0 + m - 1 of u, taken once per value as a 32-bit window), so b slices cost ⌈b/16⌉ reads of
+// the column: ⌈b/16⌉·n·w_c bytes read + b·n/8 written.
+struct SliceBuildArgs {
+    uint64_t* out[kMultiKeys];
+    int64_t base;
+    uint32_t s0, m;
+};
+
+template <typename T, int M, int FK = 0>
+__global__ __launch_bounds__(256) void bitslice_build_kernel(const T* __restrict__ col,
+                                                             const uint64_t* __restrict__ validity, uint64_t n_rows,
+                                                             uint64_t n_words_padded, SliceBuildArgs a) {
+    static_assert(M >= 1 && M <= kMultiKeys, "slices per pass");
+    constexpr int JB = 16;
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave_id = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t w0 = wave_id * 64; w0 < n_words_padded; w0 += n_waves * 64) {
+        uint32_t lo[M], hi[M];  // lane j keeps word j of every slice
+#pragma unroll
+        for (int k = 0; k < M; ++k) lo[k] = hi[k] = 0;
+        for (int jb = 0; jb < 64; jb += JB) {
+            uint32_t v[JB];  // bits s0 … s0 + 31 of u
+            bool ok[JB];
+#pragma unroll
+            for (int j = 0; j < JB; ++j) {
+                const uint64_t row = (w0 + jb + j) * 64 + lane;
+                ok[j] = row < n_rows;
+                const int64_t key = ok[j] ? (int64_t)key_of<FK>(__builtin_nontemporal_load(col + row)) : a.base;
+                v[j] = (uint32_t)(((uint64_t)key - (uint64_t)a.base) >> a.s0);
+                if (validity) ok[j] = ok[j] && ((validity[w0 + jb + j] >> lane) & 1ull);
+            }
+#pragma unroll
+            for (int j = 0; j < JB; ++j) {
+                const uint64_t okm = __ballot(ok[j]);
+                uint64_t b[M];
+#pragma unroll
+                for (int k = 0; k < M; ++k) b[k] = __ballot((v[j] >> k) & 1u) & okm;
+                if (lane == jb + j) {
+#pragma unroll
+                    for (int k = 0; k < M; ++k) {
+                        lo[k] = (uint32_t)b[k];
+                        hi[k] = (uint32_t)(b[k] >> 32);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < M; ++k)
+            if (k < (int)a.m) a.out[k][w0 + lane] = ((uint64_t)hi[k] << 32) | lo[k];
+    }
+}
+
+// After a merge: the words holding a merged row, sliced again. A wave walks 64 records (rows
+// ascend); the first record of each 64-row word makes the wave load that word's 64 values and
+// ballot every slice, lane 0 storing the word. The build kernel restricted to those words.
+template <typename T, int FK = 0>
+__global__ __launch_bounds__(256) void bitslice_reslice_kernel(const int64_t* __restrict__ rows, uint64_t m,
+                                                               const T* __restrict__ col,
+                                                               const uint64_t* __restrict__ validity, uint64_t n_rows,
+                                                               int64_t base, uint32_t n_slices, SliceSet sl) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave_id = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t i0 = wave_id * 64; i0 < m; i0 += n_waves * 64) {
+        const uint64_t i1 = i0 + 64 < m ? i0 + 64 : m;
+        for (uint64_t i = i0; i < i1; ++i) {
+            const uint64_t r = (uint64_t)rows[i];
+            if (r >= n_rows) continue;
+            const uint64_t word = r >> 6;
+            if (i > 0 && ((uint64_t)rows[i - 1] >> 6) == word) continue;  // this word is done
+            const uint64_t row = word * 64 + lane;
+            bool ok = row < n_rows;
+            const int64_t key = ok ? (int64_t)key_of<FK>(col[row]) : base;
+            const uint64_t u = (uint64_t)key - (uint64_t)base;
+            if (validity) ok = ok && ((validity[word] >> lane) & 1ull);
+            const uint64_t okm = __ballot(ok);
+            for (uint32_t s = 0; s < n_slices; ++s) {
+                const uint64_t bits = __ballot((u >> s) & 1ull) & okm;
+                if (lane == 0) sl.s[s][word] = bits;
+            }
+        }
+    }
+}
+
+// Compare: out = valid ∧ (lo <= u <= hi), u read from the slices; `negate` complements under
+// valid (!=). One pass from slice b - 1 down to 0 carrying, per word, (gt, eq) against lo and
+// (lt, eq) against hi: at a slice w, a 1 bit of lo keeps eq only where w is 1, a 0 bit moves
+// eq ∧ w to gt; hi mirrored. lo and hi are kernel arguments, so the branch on each constant bit
+// is scalar. Shaped like candidate_check_kernel: each thread owns two consecutive words (16-byte
+// loads and one 16-byte store), and a chunk of up to 8 slices is loaded (streamed once:
+// non-temporal) before the ripple consumes it. LO / HI: the sides the bound needs (lo > 0,
+// hi < 2^b - 1). Traffic: (b + 1 [+ 1 with validity])·n/8 bytes.
+template <bool LO, bool HI, int CNT>
+__device__ __forceinline__ void ripple_chunk(const SliceSet& sl, int top, uint64_t p, uint64_t lo, uint64_t hi,
+                                             u64x2& gt, u64x2& eql, u64x2& lt, u64x2& eqh) {
+    u64x2 w[CNT];
+#pragma unroll
+    for (int j = 0; j < CNT; ++j) w[j] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(sl.s[top - j]) + p);
+#pragma unroll
+    for (int j = 0; j < CNT; ++j) {
+        const int s = top - j;
+        if (LO) {
+            if ((lo >> s) & 1ull) {
+                eql &= w[j];
+            } else {
+                gt |= eql & w[j];
+                eql &= ~w[j];
+            }
+        }
+        if (HI) {
+            if ((hi >> s) & 1ull) {
+                lt |= eqh & ~w[j];
+                eqh &= w[j];
+            } else {
+                eqh &= ~w[j];
+            }
+        }
+    }
+}
+
+template <bool LO, bool HI>
+__global__ __launch_bounds__(256) void bitslice_compare_kernel(SliceSet sl, uint32_t n_slices,
+                                                               const uint64_t* __restrict__ validity, uint64_t n_rows,
+                                                               uint64_t n_words_padded, uint64_t lo, uint64_t hi,
+                                                               int negate, uint64_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t n_words = (n_rows + 63) / 64;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; 2 * p < n_words_padded; p += stride) {
+        const uint64_t w0 = 2 * p;
+        // the valid rows: full words, the tail word's rows, nothing past it (validity is read only
+        // below n_words: a caller's mask need not be padded)
+        u64x2 valid;
+        valid.x = w0 < n_words ? ~0ull : 0ull;
+        valid.y = w0 + 1 < n_words ? ~0ull : 0ull;
+        if (w0 + 1 == n_words && (n_rows & 63)) valid.x = (1ull << (n_rows & 63)) - 1;
+        if (w0 + 2 == n_words && (n_rows & 63)) valid.y = (1ull << (n_rows & 63)) - 1;
+        if (validity) {
+            if (w0 + 1 < n_words) valid &= reinterpret_cast<const u64x2*>(validity)[p];
+            else if (w0 < n_words) valid.x &= validity[w0];
+        }
+        u64x2 res = valid;
+        if ((LO || HI) && w0 < n_words) {
+            u64x2 gt = {0ull, 0ull}, lt = {0ull, 0ull}, eql = {~0ull, ~0ull}, eqh = {~0ull, ~0ull};
+            int top = (int)n_slices - 1;
+            switch (n_slices & 7u) {  // the top slices that fill no chunk of 8, then whole chunks
+            case 1: ripple_chunk<LO, HI, 1>(sl, top, p, lo, hi, gt, eql, lt, eqh); break;
+            case 2: ripple_chunk<LO, HI, 2>(sl, top, p, lo, hi, gt, eql, lt, eqh); break;
+            case 3: ripple_chunk<LO, HI, 3>(sl, top, p, lo, hi, gt, eql, lt, eqh); break;
+            case 4: ripple_chunk<LO, HI, 4>(sl, top, p, lo, hi, gt, eql, lt, eqh); break;
+            case 5: ripple_chunk<LO, HI, 5>(sl, top, p, lo, hi, gt, eql, lt, eqh); break;
+            case 6: ripple_chunk<LO, HI, 6>(sl, top, p, lo, hi, gt, eql, lt, eqh); break;
+            case 7: ripple_chunk<LO, HI, 7>(sl, top, p, lo, hi, gt, eql, lt, eqh); break;
+            default: break;
+            }
+            top -= (int)(n_slices & 7u);
+            for (; top >= 7; top -= 8) ripple_chunk<LO, HI, 8>(sl, top, p, lo, hi, gt, eql, lt, eqh);
+            if (LO) res &= gt | eql;
+            if (HI) res &= lt | eqh;
+        }
+        if (negate) res = valid & ~res;
+        reinterpret_cast<u64x2*>(out)[p] = res;
+    }
+}
+
 // ------------------------------------------------------------------ index build: column stats
 
 // min / max / any-valid of a column (the statistics an index build needs; the reference
@@ -3632,6 +3807,96 @@ hipError_t launch_compare_bitvectors(const void* col, int type, const uint64_t* 
     if (a.m <= 4) return launch_compare_m<4>(col, type, validity, n_rows, cmp, a, stream);
     if (a.m <= 8) return launch_compare_m<8>(col, type, validity, n_rows, cmp, a, stream);
     return launch_compare_m<kMultiKeys>(col, type, validity, n_rows, cmp, a, stream);
+}
+
+namespace {
+template <typename T, int FK>
+void bitslice_build_pass(const T* col, const uint64_t* validity, uint64_t n_rows, const SliceBuildArgs& a,
+                         hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
+    const uint64_t nw = padded_words(n_rows);
+    const uint64_t blocks = std::min<uint64_t>((nw / 64 + 3) / 4, 8192);
+    const dim3 grid((unsigned)std::max<uint64_t>(blocks, 1)), block(256);
+    // the smallest slice count that covers m: the ballots per word grow with it
+    if (a.m <= 4)
+        hipExtLaunchKernelGGL((bitslice_build_kernel<T, 4, FK>), grid, block, 0, stream, e0, e1, 0, col, validity, n_rows,
+                              nw, a);
+    else if (a.m <= 8)
+        hipExtLaunchKernelGGL((bitslice_build_kernel<T, 8, FK>), grid, block, 0, stream, e0, e1, 0, col, validity, n_rows,
+                              nw, a);
+    else
+        hipExtLaunchKernelGGL((bitslice_build_kernel<T, kMultiKeys, FK>), grid, block, 0, stream, e0, e1, 0, col,
+                              validity, n_rows, nw, a);
+}
+}  // namespace
+
+hipError_t launch_bitslice_build(const void* col, int type, const uint64_t* validity, uint64_t n_rows, int64_t base,
+                                 uint32_t n_slices, const SliceSet& out, hipStream_t stream, hipEvent_t ev0,
+                                 hipEvent_t ev1) {
+    if (n_slices > kMaxSlices) return hipErrorInvalidValue;
+    for (uint32_t s0 = 0; s0 < n_slices; s0 += kMultiKeys) {
+        SliceBuildArgs a{};
+        a.base = base;
+        a.s0 = s0;
+        a.m = std::min<uint32_t>(kMultiKeys, n_slices - s0);
+        for (uint32_t k = 0; k < a.m; ++k) a.out[k] = out.s[s0 + k];
+        hipEvent_t e0 = s0 == 0 ? ev0 : nullptr, e1 = s0 + kMultiKeys >= n_slices ? ev1 : nullptr;
+        if (type == kTypeFloat)
+            bitslice_build_pass<int32_t, 1>(static_cast<const int32_t*>(col), validity, n_rows, a, stream, e0, e1);
+        else if (type == kTypeDouble)
+            bitslice_build_pass<int64_t, 2>(static_cast<const int64_t*>(col), validity, n_rows, a, stream, e0, e1);
+        else if (type == kTypeUInt64)
+            bitslice_build_pass<int64_t, 3>(static_cast<const int64_t*>(col), validity, n_rows, a, stream, e0, e1);
+        else if (type_is32(type))
+            bitslice_build_pass<int32_t, 0>(static_cast<const int32_t*>(col), validity, n_rows, a, stream, e0, e1);
+        else
+            bitslice_build_pass<int64_t, 0>(static_cast<const int64_t*>(col), validity, n_rows, a, stream, e0, e1);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_bitslice_reslice(const int64_t* rows, uint64_t m, const void* col, int type, const uint64_t* validity,
+                                   uint64_t n_rows, int64_t base, uint32_t n_slices, const SliceSet& slices,
+                                   hipStream_t stream) {
+    if (n_slices > kMaxSlices) return hipErrorInvalidValue;
+    if (m == 0 || n_slices == 0) return hipSuccess;
+    const dim3 grid(grid_for(m)), block(256);  // a wave per 64 records
+#define CUBIT_RESLICE(T, FK)                                                                                        \
+    hipLaunchKernelGGL((bitslice_reslice_kernel<T, FK>), grid, block, 0, stream, rows, m, static_cast<const T*>(col), \
+                       validity, n_rows, base, n_slices, slices)
+    if (type == kTypeFloat) CUBIT_RESLICE(int32_t, 1);
+    else if (type == kTypeDouble) CUBIT_RESLICE(int64_t, 2);
+    else if (type == kTypeUInt64) CUBIT_RESLICE(int64_t, 3);
+    else if (type_is32(type)) CUBIT_RESLICE(int32_t, 0);
+    else CUBIT_RESLICE(int64_t, 0);
+#undef CUBIT_RESLICE
+    return hipGetLastError();
+}
+
+hipError_t launch_bitslice_compare(const SliceSet& slices, uint32_t n_slices, const uint64_t* validity, uint64_t n_rows,
+                                   uint64_t lo, uint64_t hi, int negate, uint64_t* out, hipStream_t stream,
+                                   hipEvent_t ev0, hipEvent_t ev1) {
+    if (n_slices > kMaxSlices) return hipErrorInvalidValue;
+    const uint64_t max = n_slices >= 64 ? ~0ull : (1ull << n_slices) - 1;
+    // an interval that holds no offset is the complement of the one that holds them all
+    if (lo > hi || lo > max) {
+        lo = 0;
+        hi = max;
+        negate = !negate;
+    }
+    if (hi > max) hi = max;
+    const bool need_lo = lo != 0, need_hi = hi != max;
+    const uint64_t nw = padded_words(n_rows);
+    const dim3 grid((unsigned)std::min<uint64_t>((nw / 2 + 255) / 256, 8192)), block(256);
+#define CUBIT_SLICED(L, H)                                                                                         \
+    hipExtLaunchKernelGGL((bitslice_compare_kernel<L, H>), grid, block, 0, stream, ev0, ev1, 0, slices, n_slices, \
+                          validity, n_rows, nw, lo, hi, negate ? 1 : 0, out)
+    if (need_lo && need_hi) CUBIT_SLICED(true, true);
+    else if (need_lo) CUBIT_SLICED(true, false);
+    else if (need_hi) CUBIT_SLICED(false, true);
+    else CUBIT_SLICED(false, false);
+#undef CUBIT_SLICED
+    return hipGetLastError();
 }
 
 hipError_t launch_column_minmax(const void* col, int type, const uint64_t* validity, uint64_t n_rows, int64_t* out3,

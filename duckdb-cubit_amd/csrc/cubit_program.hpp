@@ -88,6 +88,46 @@ inline CmpRange cmp_range(int cmp, int64_t constant, int64_t constant2) {
     return r;
 }
 
+// A comparison against a key constant as a bit-sliced index (CUBIT_INDEX_SLICED) answers it. The
+// index holds `bits` slices of u = (uint64)key - (uint64)base, so its valid rows' keys lie in
+// [base, base + 2^bits - 1]. cmp is CUBIT_CMP_* (0 … 5, c2 unused) or 6, the half-open c <= v < c2.
+// kInterval: the passing keys are those with lo <= u <= hi, or with negate set (!=) the others;
+// kFalse / kAllValid: no key of that range passes / every one does. All arithmetic is unsigned:
+// k ↦ (uint64)k ^ 2^63 keeps the signed order, so offsets of INT64_MIN / INT64_MAX constants and a
+// 64-bit span never overflow.
+struct SlicedInterval {
+    enum Kind { kFalse, kAllValid, kInterval } kind = kFalse;
+    uint64_t lo = 0, hi = 0;
+    bool negate = false;
+};
+// the bit length of top - base (0: one value, 64: INT64_MIN … INT64_MAX)
+inline uint32_t sliced_bits(int64_t base, int64_t top) {
+    const uint64_t span = (uint64_t)top - (uint64_t)base;
+    return span ? 64u - (uint32_t)__builtin_clzll(span) : 0u;
+}
+inline SlicedInterval sliced_interval(int cmp_or_between, int64_t c, int64_t c2, int64_t base, uint32_t bits) {
+    const CmpRange r = cmp_range(cmp_or_between, c, c2);
+    const bool neg = r.neg != 0;
+    SlicedInterval none, all;
+    none.kind = neg ? SlicedInterval::kAllValid : SlicedInterval::kFalse;
+    all.kind = neg ? SlicedInterval::kFalse : SlicedInterval::kAllValid;
+    if (r.empty() || r.hi < base) return none;
+    constexpr uint64_t kBias = 0x8000000000000000ull;
+    const uint64_t ub = (uint64_t)base ^ kBias;
+    const uint64_t max = bits >= 64 ? ~0ull : (1ull << bits) - 1;
+    const uint64_t lo = r.lo <= base ? 0 : ((uint64_t)r.lo ^ kBias) - ub;
+    uint64_t hi = ((uint64_t)r.hi ^ kBias) - ub;  // r.hi >= base
+    if (lo > max) return none;
+    if (hi > max) hi = max;
+    if (lo == 0 && hi == max) return all;
+    SlicedInterval s;
+    s.kind = SlicedInterval::kInterval;
+    s.lo = lo;
+    s.hi = hi;
+    s.negate = neg;
+    return s;
+}
+
 // One past the last node of the subtree rooted at node i of a prefix-order node array, or -1 when
 // the array ends inside it. A negative child count reads as none.
 inline int filter_subtree_end(const cubit_filter_node* nodes, uint32_t n_nodes, uint32_t i) {

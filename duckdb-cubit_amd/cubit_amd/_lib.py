@@ -50,7 +50,7 @@ def fp_bits(values, type_: int):
     return _np.ascontiguousarray(_np.asarray(values, dtype=_np.int64))
 CMP_EQ, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE = range(6)
 FILTER_CONSTANT, FILTER_IS_NULL, FILTER_IS_NOT_NULL, FILTER_OR, FILTER_AND = range(5)
-INDEX_RANGE, INDEX_EQUALITY, INDEX_BINS = 0, 1, 2
+INDEX_RANGE, INDEX_EQUALITY, INDEX_BINS, INDEX_SLICED = 0, 1, 2, 3
 SUM_GATHER_B = 1
 SUM_NO_ZONEMAP = 2
 SUM_PACKED_A = 4
@@ -130,6 +130,8 @@ GPU_SIGNATURES = {
     "cubit_copy_stream_wait_event": (C.c_int, [_P, _P, _P]),
     "cubit_copy_event_destroy": (C.c_int, [_P, _P]),
     "cubit_build_bitvector": (C.c_int, [_P, _P, C.c_int, _P, _U64, C.c_int, _I64, _P]),
+    "cubit_bitslice_build": (C.c_int, [_P, _P, C.c_int, _P, _U64, _I64, _U32, _P]),
+    "cubit_bitslice_compare": (C.c_int, [_P, _P, _U32, _P, _U64, _U64, _U64, C.c_int, _P]),
     "cubit_dict_create": (C.c_int, [_P, _P, _U64, C.POINTER(_P)]),
     "cubit_dict_destroy": (C.c_int, [_P]),
     "cubit_dict_size": (C.c_int, [_P, C.POINTER(_U64)]),
@@ -176,6 +178,8 @@ GPU_SIGNATURES = {
     "cubit_table_last_zones": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U32)]),
     "cubit_table_use_packed_filter": (C.c_int, [_P, C.c_int]),
     "cubit_table_last_packed": (C.c_int, [_P, C.POINTER(_U32)]),
+    "cubit_table_use_sliced": (C.c_int, [_P, C.c_int]),
+    "cubit_table_last_sliced": (C.c_int, [_P, C.POINTER(_U32)]),
     "cubit_table_use_narrowing": (C.c_int, [_P, C.c_int]),
     "cubit_table_last_narrowed": (C.c_int, [_P, C.POINTER(_U32)]),
     "cubit_table_last_k0_order": (C.c_int, [_P, C.POINTER(C.c_int32), _U32, C.POINTER(_U32)]),

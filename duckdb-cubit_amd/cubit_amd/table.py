@@ -632,6 +632,18 @@ class CubitTable:
         L.check(self.lib.cubit_table_last_packed(self.handle, C.byref(v)))
         return int(v.value)
 
+    def use_sliced(self, on: bool = True) -> None:
+        """Answer whole-column (K0) comparisons of a column with a bit-sliced index
+        (build_index(col, L.INDEX_SLICED)) from its slices where they move fewer bytes (the
+        default), or from the plain column. Results are identical either way."""
+        L.check(self.lib.cubit_table_use_sliced(self.handle, 1 if on else 0))
+
+    def last_sliced(self) -> int:
+        """Leaves the last scan / sum_product built from a bit-sliced index."""
+        v = C.c_uint32()
+        L.check(self.lib.cubit_table_last_sliced(self.handle, C.byref(v)))
+        return int(v.value)
+
     def use_narrowing(self, on: bool = True) -> None:
         """Read unindexed (K0) comparison columns of a conjunction only at the rows its other
         filters keep, when they keep few (the default), or always in full."""

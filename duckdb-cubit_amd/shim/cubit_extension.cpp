@@ -79,10 +79,11 @@ namespace duckdb {
 
 // A bitmap index the attach builds on one column (cubit_table_build_index): its encoding and
 // keys (empty = every distinct value of the column), or the number of equi-depth bins whose edges
-// each partition chooses from its rows (cubit_table_build_index_quantiles).
+// each partition chooses from its rows (cubit_table_build_index_quantiles). `column=sliced` is a
+// bit-sliced index: it has no keys and goes to cubit_table_build_index as it is.
 struct CubitIndexSpec {
     column_t column;
-    int encoding;  // CUBIT_INDEX_RANGE / _EQUALITY / _BINS
+    int encoding;  // CUBIT_INDEX_RANGE / _EQUALITY / _BINS / _SLICED
     vector<int64_t> keys;
     vector<string> str_keys;  // a VARCHAR column's keys (sorted, distinct)
     uint32_t quantile_bins = 0;  // `column=encoding~count`: no keys, count bins

@@ -393,15 +393,16 @@ inline void PackStrings(const std::vector<std::string> &strs, std::vector<char> 
 // ------------------------------------------------------------------ index specification
 
 // Index specification of cubit_attach's third argument: `column=encoding[:v1,v2,…]` or
-// `column=encoding~count` items separated by ';' — encoding range | equality | bins, values as SQL
+// `column=encoding~count` items separated by ';' — encoding range | equality | bins | sliced (a
+// bit-sliced index: no literal list and no count), values as SQL
 // literals of the column's type (dates, decimals); `~count` (range and bins only, 2 … 1,024, no
 // literal list beside it) asks for that many equi-depth bins, their edges chosen from the column's
 // quantiles (cubit_table_build_index_quantiles), e.g.
 //   'l_shipdate=range:1994-01-01,1995-01-01;l_shipdate=bins:1992-01-01,1993-01-01,…;l_discount=range'
-//   'l_shipdate=range~64;l_extendedprice=bins~256'
+//   'l_shipdate=range~64;l_extendedprice=bins~256;l_shipdate=sliced'
 struct IndexItem {
     std::string name;  // the column, not yet resolved
-    int encoding;      // CUBIT_INDEX_RANGE / _EQUALITY / _BINS
+    int encoding;      // CUBIT_INDEX_RANGE / _EQUALITY / _BINS / _SLICED
     std::vector<std::string> literals;  // not yet cast; empty = every distinct value
     uint32_t quantile_bins = 0;  // `~count`: the equi-depth bins to choose edges for (0 = none asked)
 };
@@ -451,7 +452,8 @@ inline void TrimText(std::string &s) {
 // The items of `spec` in order (empty items skipped, whitespace around items, names, encodings and
 // literals dropped, encodings in any letter case). At the first malformed item the split stops:
 // `items` holds the ones before it, `bad` the offending text — the item without a '=', the
-// encoding that is none of the three (`equality~8` among them: an equality index takes no count),
+// encoding that is none of the four (`equality~8`, `sliced~8` and `sliced:1` among them: an equality
+// index takes no count, a bit-sliced one neither a count nor literals),
 // or the count as written, with what follows it (`1025`, `x`, `8:1,2`).
 inline SpecStatus SplitIndexSpec(const std::string &spec, std::vector<IndexItem> &items, std::string &bad) {
     items.clear();
@@ -499,6 +501,12 @@ inline SpecStatus SplitIndexSpec(const std::string &spec, std::vector<IndexItem>
             ix.encoding = CUBIT_INDEX_EQUALITY;
         } else if (enc == "bins") {
             ix.encoding = CUBIT_INDEX_BINS;
+        } else if (enc == "sliced" && colon == std::string::npos) {
+            ix.encoding = CUBIT_INDEX_SLICED;
+        } else if (enc == "sliced") {
+            bad = rest;
+            TrimText(bad);
+            return SpecStatus::UnknownEncoding;
         } else {
             bad = enc;
             return SpecStatus::UnknownEncoding;

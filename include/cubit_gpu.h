@@ -151,6 +151,17 @@ static inline int64_t cubit_fp_value(int type, int64_t key) {
 #define CUBIT_INDEX_BINS 2      /* B_i = {valid rows with edge_i <= v < edge_i+1}: kept beside a range or
                                    equality index on the same column; a range whose bounds are bin
                                    edges reads its bins instead of two range bitvectors when fewer */
+/* A bit-sliced index (O'Neil & Quass, SIGMOD 1997; Rinfret, O'Neil & O'Neil, SIGMOD 2001): a secondary
+ * index kept beside a column's RANGE / EQUALITY index and its BINS index. With k_r the comparison
+ * key of row r (cubit_fp_key of the stored value; a dictionary column's code), base / top the
+ * smallest / largest key over the valid rows and b the bit length of (uint64)top - (uint64)base (0
+ * when one value is present, 64 for INT64_MIN ... INT64_MAX): slice s (0 <= s < b) is a table-owned
+ * bitvector whose bit r = valid(r) && ((((uint64)k_r - (uint64)base) >> s) & 1). NULL rows are 0 in
+ * every slice, padding is 0; a column with no valid row, or an empty partition, gets an empty index
+ * with no slices. Any comparison with a constant is a ripple of AND / OR / ANDNOT over the slices'
+ * 64-row words from the top slice down, exact for every constant: it answers what would otherwise be
+ * a whole-column K0 pass, reading b/8 bytes per row. Memory: b * n_rows / 8 bytes. */
+#define CUBIT_INDEX_SLICED 3
 
 /* ---- bitvector program opcodes (operands >= 0 are leaf indices, postfix order) */
 #define CUBIT_OP_AND (-1)
@@ -316,6 +327,23 @@ int cubit_build_bitvector(cubit_ctx *ctx, const void *d_col, int type, const uin
                           int cmp, int64_t constant, uint64_t *d_words);
 /* words per bitvector including tile padding */
 uint64_t cubit_padded_words(uint64_t n_rows);
+/* The kernels of a bit-sliced index (CUBIT_INDEX_SLICED), as cubit_build_bitvector is K0's. d_slices
+ * is a host array of n_slices (0 ... 64) device pointers, least significant slice first, each
+ * cubit_padded_words(n_rows) words, every word written (padding zeroed).
+ * cubit_bitslice_build: slice s gets bit s of (uint64)key - (uint64)base of every valid row, `base`
+ * given as a comparison key (cubit_fp_key of a FLOAT / DOUBLE pattern, value ^ 2^63 for UINT64). A
+ * row whose key - base does not fit n_slices bits is the caller's error: its high bits are dropped
+ * (a table's index never holds one). One pass of the column per 16 slices.
+ * cubit_bitslice_compare: d_words = valid AND (lo <= u <= hi), u the row's offset read from the
+ * slices, lo / hi unsigned offsets from the base; negate != 0 gives valid AND NOT (lo <= u <= hi).
+ * lo > hi is the empty interval. d_validity NULL = every row below n_rows is valid; it is read only
+ * below ceil(n_rows / 64) words. Slices, validity and d_words must be 16-byte aligned.
+ * Both run on the context's stream; with timing on each call is one timed launch. */
+int cubit_bitslice_build(cubit_ctx *ctx, const void *d_col, int type, const uint64_t *d_validity, uint64_t n_rows,
+                         int64_t base, uint32_t n_slices, uint64_t *const *d_slices);
+int cubit_bitslice_compare(cubit_ctx *ctx, const uint64_t *const *d_slices, uint32_t n_slices,
+                           const uint64_t *d_validity, uint64_t n_rows, uint64_t lo, uint64_t hi, int negate,
+                           uint64_t *d_words);
 
 /* K1+K2 — evaluate a postfix program over `n_leaves` device bitvectors (each
  * cubit_padded_words(n_rows) words; leaf_negate bit k complements leaf k before use) and
@@ -472,6 +500,16 @@ int cubit_table_add_segment_column(cubit_table *t, int col, int type, const uint
  * plain column stays). cubit_table_last_packed: leaves the last scan built so. */
 int cubit_table_use_packed_filter(cubit_table *t, int on);
 int cubit_table_last_packed(cubit_table *t, uint32_t *n_leaves);
+/* A column with a bit-sliced index (cubit_table_build_index(t, col, CUBIT_INDEX_SLICED, NULL, 0))
+ * answers a constant comparison that would otherwise be a whole-column K0 pass from its slices,
+ * when they move fewer bytes: (b + 2) / 8 per row against the column's 4 or 8. The leaf is bit for
+ * bit K0's, so zonemaps, narrowing estimates and MVCC patches are unchanged; index leaves,
+ * candidate checks, equality unions, bins and narrowed (masked) compares stay as they are. On a
+ * column whose only index is bit-sliced, the constant bounds of a conjunction (a <= x AND x < b)
+ * fold into one leaf, one pass over the slices. On by default; results are identical either way.
+ * cubit_table_last_sliced: leaves the last scan / sum_product built from slices. */
+int cubit_table_use_sliced(cubit_table *t, int on);
+int cubit_table_last_sliced(cubit_table *t, uint32_t *n_leaves);
 /* Selection narrowing (on by default): in a conjunction, a constant comparison on a column the
  * index cannot answer (K0) reads its column only at the rows the rest of the conjunction keeps,
  * when that is at most one row in 32 — the reference's filter loop reading each later filter
@@ -489,7 +527,11 @@ int cubit_table_last_narrowed(cubit_table *t, uint32_t *n_leaves);
 int cubit_table_last_k0_order(cubit_table *t, int32_t *cols, uint32_t cap, uint32_t *n);
 /* Build a bitmap index on `col` (K0). edges/values sorted ascending; n = 0 means "all
  * distinct values of the column" (exact for every constant). RANGE / EQUALITY replace the
- * column's primary index; BINS (n >= 2 edges) adds a secondary binned index. */
+ * column's primary index; BINS (n >= 2 edges) adds a secondary binned index; SLICED (n must be 0:
+ * CUBIT_ERR_INVALID otherwise) adds the secondary bit-sliced index. Like every index it is
+ * maintained in place: an append slices the new rows and splices them in (a key above the top adds
+ * all-zero high slices first; a key below the base rebuilds the slices in one build), merges and
+ * syncs re-slice the 64-row words that hold a changed row, and re-registering the column drops it. */
 int cubit_table_build_index(cubit_table *t, int col, int encoding, const int64_t *values, uint32_t n);
 /* Build a RANGE or BINS index on `col` whose edges are the column's equi-depth quantiles, chosen
  * on the GPU by a radix select over the column where it lies (a few streaming histogram passes; the
@@ -520,14 +562,16 @@ int cubit_table_build_index_quantiles(cubit_table *t, int col, int encoding, uin
 /* Number of bitvectors and bytes held by the indexes on col, all encodings (0 if none). */
 int cubit_table_index_info(cubit_table *t, int col, uint32_t *n_bitvectors, uint64_t *bytes);
 /* Index persistence (the reference persists index state through IndexStorageInfo,
- * bound_index.hpp:117-118): write a column's RANGE / EQUALITY / BINS index (keys,
+ * bound_index.hpp:117-118): write a column's RANGE / EQUALITY / BINS / SLICED index (keys,
  * statistics, bitvectors) to one file, and load it back into a partition of the same size
  * (it replaces that encoding's index on the column). The file does not carry the column
  * data: load it only beside the column it was built from. It names the column's type and, for a
  * dictionary column (VARCHAR, HUGEINT / UHUGEINT), its dictionary (a fingerprint of the entries):
  * a load onto a column of another type or against another dictionary is refused
  * (CUBIT_ERR_INVALID). A version-1 file names neither and holds raw values as keys: it loads onto
- * an INT32 / INT64 column only (UBIGINT, FLOAT and DOUBLE indexes are keyed by comparison keys). */
+ * an INT32 / INT64 column only (UBIGINT, FLOAT and DOUBLE indexes are keyed by comparison keys).
+ * A SLICED index is saved with no keys and one bitvector per slice; a file whose bitvector count is
+ * not the bit length of vmax - vmin is refused. */
 int cubit_table_save_index(cubit_table *t, int col, int encoding, const char *path);
 int cubit_table_load_index(cubit_table *t, int col, const char *path);
 
