@@ -80,6 +80,7 @@ struct cubit_ctx {
     int64_t* tmp_ids = nullptr;
     uint64_t tmp_cap = 0;
     int64_t* partials = nullptr;
+    int64_t* agg = nullptr;      // workspace of the aggregate kernels (kAggWorkspace int64)
     uint64_t* ticket = nullptr;  // claim ticket of the evaluate kernels (EvalArgs::ticket)
     uint64_t* flags = nullptr;   // look-back flag words of eval_decode_lookback (EvalArgs::flags)
     uint64_t epoch = 0;          // the last look-back launch's epoch (EvalArgs::epoch)
@@ -356,12 +357,14 @@ int cubit_ctx_create(int device, cubit_ctx** out) {
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
         ctx->n_cus = prop.multiProcessorCount;
     if (hipMalloc(&ctx->partials, 2 * kSumBlocks * sizeof(int64_t)) != hipSuccess ||
+        hipMalloc(&ctx->agg, kAggWorkspace * sizeof(int64_t)) != hipSuccess ||
         hipMalloc(&ctx->ticket, kTicketWords * sizeof(uint64_t)) != hipSuccess ||
         hipMemset(ctx->ticket, 0, kTicketWords * sizeof(uint64_t)) != hipSuccess ||
         hipMalloc(&ctx->flags, kLookbackMaxTiles * sizeof(uint64_t)) != hipSuccess ||
         hipMemset(ctx->flags, 0, kLookbackMaxTiles * sizeof(uint64_t)) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess) {
         if (ctx->partials) (void)hipFree(ctx->partials);
+        if (ctx->agg) (void)hipFree(ctx->agg);
         if (ctx->ticket) (void)hipFree(ctx->ticket);
         if (ctx->flags) (void)hipFree(ctx->flags);
         delete ctx;
@@ -378,6 +381,7 @@ int cubit_ctx_destroy(cubit_ctx* ctx) {
     if (ctx->dst_off) (void)hipFree(ctx->dst_off);
     if (ctx->tmp_ids) (void)hipFree(ctx->tmp_ids);
     if (ctx->partials) (void)hipFree(ctx->partials);
+    if (ctx->agg) (void)hipFree(ctx->agg);
     if (ctx->ticket) (void)hipFree(ctx->ticket);
     if (ctx->flags) (void)hipFree(ctx->flags);
     if (ctx->live_pending) (void)hipEventSynchronize(ctx->live_ev);
@@ -729,6 +733,48 @@ int cubit_bitslice_compare(cubit_ctx* ctx, const uint64_t* const* d_slices, uint
     return CUBIT_OK;
 }
 
+int cubit_bitslice_aggregate(cubit_ctx* ctx, const uint64_t* const* d_slices, uint32_t n_slices,
+                             const uint64_t* d_validity, const uint64_t* d_filter, uint64_t n_rows, int type,
+                             int64_t base, uint32_t ops, int64_t* d_out) {
+    if (!ctx || !d_out || (n_slices && !d_slices)) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(ctx);
+    if (n_slices > kMaxSlices) return fail(CUBIT_ERR_INVALID, "%u slices (0 … 64)", n_slices);
+    if (ops & ~(CUBIT_AGG_SUM | CUBIT_AGG_MIN | CUBIT_AGG_MAX)) return fail(CUBIT_ERR_INVALID, "ops %u", ops);
+    if (type != CUBIT_TYPE_INT32 && type != CUBIT_TYPE_INT64 && type != CUBIT_TYPE_VARCHAR && !type_is_keyed(type))
+        return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
+    if ((ops & CUBIT_AGG_SUM) && (type_is_fp(type) || type == CUBIT_TYPE_VARCHAR))
+        return fail(CUBIT_ERR_UNSUPPORTED, "SUM of a type %d column: its keys are not linear in the value", type);
+    if (n_rows >= (1ull << 47)) return fail(CUBIT_ERR_INVALID, "%llu rows exceed 2^47", (unsigned long long)n_rows);
+    auto aligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    if (!aligned(d_filter) || !aligned(d_validity)) return fail(CUBIT_ERR_INVALID, "bitvectors must be 16-byte aligned");
+    SliceAggArgs g{};
+    for (uint32_t s = 0; s < n_slices; ++s) {
+        if (!d_slices[s] || !aligned(d_slices[s])) return fail(CUBIT_ERR_INVALID, "slice %u is null or unaligned", s);
+        g.slices.s[s] = const_cast<uint64_t*>(d_slices[s]);
+    }
+    if (int rc = set_device(ctx)) return rc;
+    if (n_rows == 0) {  // no rows: zero counts, nothing to launch
+        HIP_CHECK(hipMemsetAsync(d_out, 0, 6 * sizeof(int64_t), ctx->stream));
+        return CUBIT_OK;
+    }
+    g.n_slices = n_slices;
+    g.validity = d_validity;
+    g.workspace = ctx->agg;
+    EvalArgs a{};
+    if (d_filter) {  // a one-leaf program; NULL: the zero-leaf form, every row below n_rows
+        a.prog.leaf[0] = d_filter;
+        a.prog.n_leaves = 1;
+    }
+    a.n_rows = n_rows;
+    a.n_words = (n_rows + 63) / 64;
+    a.ticket = ctx->ticket;
+    a.num_tiles = (uint32_t)((a.n_words + kAggTileWords - 1) / kAggTileWords);  // the tiles that hold rows
+    hipEvent_t e0, e1;
+    if (int rc = timing_events(ctx, e0, e1)) return rc;
+    HIP_CHECK(launch_eval_slice_aggregate(a, g, ops, type, base, ctx->n_cus, d_out, ctx->stream, e0, e1));
+    return CUBIT_OK;
+}
+
 }  // extern "C"
 
 extern "C" int cubit_bitvector_eval(cubit_ctx* ctx, const uint64_t* const* d_leaves, uint32_t n_leaves,
@@ -1032,6 +1078,7 @@ struct cubit_table {
     uint32_t last_narrowed = 0;  // K0 leaves the last plan built only at the rows a mask kept
     std::vector<int32_t> last_narrow_cols;  // columns of the last plan's K0 leaves, in build order
     bool last_sum_packed = false;  // the last sum_product read a from its BITPACKING segments
+    bool last_agg_slices = false;  // the last cubit_table_aggregate read the column's slices
 };
 
 namespace {
@@ -1818,6 +1865,8 @@ int build_sliced(cubit_table* t, const Column& c, uint64_t n_rows, Index& into) 
 // time at 612 M rows and 64 slices of an 8-byte column tie with it (DESIGN.md §3,
 // scripts/sliced_timing.py).
 bool sliced_moves_fewer_bytes(uint32_t bits, uint64_t elem_bytes) { return bits + 2 < 8 * elem_bytes; }
+// (its counterpart for cubit_table_aggregate, aggregate_from_slices, is in cubit_program.hpp, where
+// the CPU test of the path rule reaches it)
 
 // CUBIT_QUANTILE_PLAIN_ADDS: the histogram passes without the wave-level pre-aggregation
 // (diagnostic; scripts/quantile_timing.py times both forms)
@@ -4722,6 +4771,117 @@ extern "C" int cubit_table_sum_product(cubit_table* t, const cubit_filter_node* 
     }
     const unsigned grid = std::min<unsigned>(a.num_tiles, sum_product_grid((unsigned)ctx->n_cus));
     HIP_CHECK(launch_eval_sum_product(a, sa, std::max(grid, 1u), d_out, ctx->stream));
+    return CUBIT_OK;
+}
+
+// SELECT sum(col), min(col), max(col), count(col), count(*) WHERE <filter>: one plan, then either the
+// fused evaluate + aggregate over the column's slices, or the plan's decode into scratch, the probe
+// (which applies the visible updates, NULL-ness included) and a reduction of the probed values —
+// the structure of cubit_table_sum_product's MVCC fallback. aggregate_from_slices
+// (cubit_program.hpp) chooses; both give the same six numbers.
+extern "C" int cubit_table_aggregate(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_nodes,
+                                     const cubit_txn* txn, int col, uint32_t ops, int64_t* d_out) {
+    if (!t || !d_out) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    if (n_nodes && !nodes) return fail(CUBIT_ERR_INVALID, "nodes is null");
+    constexpr uint32_t kOps = CUBIT_AGG_SUM | CUBIT_AGG_MIN | CUBIT_AGG_MAX;
+    if (ops & ~(kOps | CUBIT_AGG_FROM_SLICES | CUBIT_AGG_FROM_COLUMN | CUBIT_AGG_NO_ZONEMAP))
+        return fail(CUBIT_ERR_INVALID, "ops %u", ops);
+    const bool force_slices = (ops & CUBIT_AGG_FROM_SLICES) != 0, force_column = (ops & CUBIT_AGG_FROM_COLUMN) != 0;
+    if (force_slices && force_column) return fail(CUBIT_ERR_INVALID, "both paths forced");
+    auto cit = t->cols.find(col);
+    if (cit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column %d not registered", col);
+    const Column& c = cit->second;
+    if ((ops & CUBIT_AGG_SUM) && (type_is_fp(c.type) || c.type == CUBIT_TYPE_VARCHAR || c.dict))
+        return fail(CUBIT_ERR_UNSUPPORTED, "SUM of column %d (type %d): its keys are not linear in the value", col,
+                    c.type);
+    if (int rc = set_device(t->ctx)) return rc;
+    cubit_ctx* ctx = t->ctx;
+    ctx->last_tiles = 0;  // no row ids reach the caller, so no tile directory
+    auto sit = t->sliced.find(col);
+    auto uit = t->upd.find(col);
+    const bool visible_updates = txn && uit != t->upd.end() && uit->second.any_visible(txn);
+    const bool usable = sit != t->sliced.end() && !sit->second.empty && t->use_sliced && !visible_updates;
+    if (force_slices && !usable)
+        return fail(CUBIT_ERR_INVALID, "column %d has no usable bit-sliced index%s", col,
+                    visible_updates ? " (an update record is visible to the transaction)" : "");
+    t->last_agg_slices = false;
+    if (t->n_rows == 0) {  // empty partition: zero counts
+        t->last_leaves = t->last_passes = 0;
+        t->last_live = t->last_zones = 0;
+        t->last_sliced = 0;
+        HIP_CHECK(hipMemsetAsync(d_out, 0, 6 * sizeof(int64_t), ctx->stream));
+        return CUBIT_OK;
+    }
+    uint64_t est_rows = t->n_rows;
+    if (usable && !force_slices && !force_column)
+        if (int rc = cubit_table_estimate_rows(t, nodes, n_nodes, &est_rows)) return rc;
+    Emitter em;
+    bool empty = false;
+    std::vector<uint32_t> live;
+    t->last_zones = real_zones(t);
+    t->last_live = 0;
+    if (int rc = plan_program(t, nodes, n_nodes, txn, em, &empty, (ops & CUBIT_AGG_NO_ZONEMAP) ? nullptr : &live))
+        return rc;
+    if (empty) {  // the filter folded to FALSE (or the zonemaps rule out every zone)
+        HIP_CHECK(hipMemsetAsync(d_out, 0, 6 * sizeof(int64_t), ctx->stream));
+        return CUBIT_OK;
+    }
+    t->last_live = live.empty() ? t->last_zones : (uint32_t)live.size();
+    const uint64_t live_rows = std::min<uint64_t>(t->n_rows, (uint64_t)t->last_live * kZoneRows);
+    const uint32_t bits = usable ? (uint32_t)sit->second.bvs.size() : 0;
+    if (aggregate_from_slices(force_slices, force_column, usable, bits, em.prog.n_leaves, c.validity != nullptr,
+                              live_rows, t->n_rows, est_rows, type_is32(c.type) ? 4 : 8)) {
+        if (t->n_rows >= (1ull << 47))
+            return fail(CUBIT_ERR_INVALID, "%llu rows exceed 2^47", (unsigned long long)t->n_rows);
+        const Index& sx = sit->second;
+        SliceAggArgs g{};
+        g.slices = slice_set(sx);
+        g.n_slices = bits;
+        g.validity = c.validity;
+        g.workspace = ctx->agg;
+        EvalArgs a{};
+        a.prog = em.prog;
+        a.n_rows = t->n_rows;
+        a.n_words = (t->n_rows + 63) / 64;
+        a.row_base = t->row_base;
+        a.ticket = ctx->ticket;
+        a.num_tiles = (uint32_t)((a.n_words + kAggTileWords - 1) / kAggTileWords);
+        if (!live.empty()) {  // zonemap skip: a zone is one tile of the kernel
+            static_assert(kZoneWords == kAggTileWords, "a zone is one aggregate tile");
+            uint32_t n_live = 0;
+            if (int rc = upload_live(ctx, live, 1, &a.live, &n_live)) return rc;
+            a.num_tiles = n_live;
+        }
+        hipEvent_t e0, e1;
+        if (int rc = timing_events(ctx, e0, e1)) return rc;
+        HIP_CHECK(launch_eval_slice_aggregate(a, g, ops & kOps, c.type, sx.vmin, ctx->n_cus, d_out, ctx->stream, e0, e1));
+        t->last_agg_slices = true;
+        t->last_sliced++;
+        return CUBIT_OK;
+    }
+    // the column path: ids, probed values and their validity words in context scratch
+    const uint64_t cap = t->n_rows;
+    const uint64_t vwords = (cap + 63) / 64;
+    if (int rc = ensure_tmp(ctx, 2 * cap + vwords)) return rc;
+    int64_t* ids = ctx->tmp_ids;
+    int64_t* xv = ctx->tmp_ids + cap;
+    uint64_t* vw = reinterpret_cast<uint64_t*>(ctx->tmp_ids + 2 * cap);
+    uint64_t* count = agg_count_slot(ctx->agg);
+    // (unordered: the decode must not take tmp_ids for an ordering pass)
+    if (int rc = run_eval(ctx, em.prog, t->n_rows, t->row_base, ids, cap, count, nullptr, RunMode::kDecode, true, false,
+                          false, live.empty() ? nullptr : &live, nullptr))
+        return rc;
+    ctx->last_tiles = 0;  // the directory described ids in scratch, not a caller's buffer
+    if (int rc = probe_impl(t, col, txn, ids, count, cap, xv, vw)) return rc;
+    HIP_CHECK(launch_aggregate_arrays(xv, vw, count, cap, ops & kOps, c.type, ctx->agg, d_out, ctx->stream));
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_last_aggregate(cubit_table* t, int* from_slices) {
+    if (!t || !from_slices) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    *from_slices = t->last_agg_slices ? 1 : 0;
     return CUBIT_OK;
 }
 

@@ -193,6 +193,40 @@ hipError_t launch_bitslice_build(const void* col, int type, const uint64_t* vali
 hipError_t launch_bitslice_compare(const SliceSet& slices, uint32_t n_slices, const uint64_t* validity, uint64_t n_rows,
                                    uint64_t lo, uint64_t hi, int negate, uint64_t* out, hipStream_t stream,
                                    hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// Aggregates of a column over a program's rows, read from the column's slices (fused evaluate +
+// aggregate, eval_slice_aggregate) or reduced from probed values (aggregate_arrays_kernel). Either
+// kernel leaves kAggPartial int64 per workgroup in `partials` — {Σ lo, Σ hi, smallest offset, largest
+// offset, valid rows} — and one finishing wave combines them on the device (slice_agg_combine,
+// cubit_program.hpp) into out[0..5] = {sum_lo, sum_hi, min, max, count_valid, count_rows}, so the
+// result is ready on the stream with no host round trip, in exact integers whatever the grid and
+// the arrival order. The workspace holds kAggWorkspace int64: the partials of up to kAggMaxGrid
+// workgroups, then the qualifying-row count the kernels publish (agg_count_slot).
+constexpr int kAggPartial = 5;
+constexpr unsigned kAggMaxGrid = 1024;
+constexpr uint64_t kAggWorkspace = (uint64_t)kAggPartial * kAggMaxGrid + 2;
+__host__ __device__ inline uint64_t* agg_count_slot(int64_t* workspace) {
+    return reinterpret_cast<uint64_t*>(workspace + (uint64_t)kAggPartial * kAggMaxGrid);
+}
+struct SliceAggArgs {
+    SliceSet slices;
+    uint32_t n_slices;
+    // the aggregated column's validity: null = every row valid; read only below ceil(n_rows / 64)
+    // words (16-byte aligned, as the slices are)
+    const uint64_t* validity;
+    int64_t* workspace;
+};
+// words per tile of eval_slice_aggregate: one zone
+constexpr uint64_t kAggTileWords = 2048;
+// a.prog may hold no leaf (n_leaves = 0: every row below n_rows qualifies); a.count is set by the
+// launcher; a.num_tiles tiles of kAggTileWords words (a.live: the zones to evaluate); ops =
+// CUBIT_AGG_SUM | _MIN | _MAX; type / base: the column's type and the slices' base key
+hipError_t launch_eval_slice_aggregate(EvalArgs a, const SliceAggArgs& g, uint32_t ops, int type, int64_t base,
+                                       int n_cus, int64_t* out, hipStream_t stream, hipEvent_t ev0 = nullptr,
+                                       hipEvent_t ev1 = nullptr);
+// the same result from x[i] (the probed values as the ABI carries them, 0 at NULL rows) and valid
+// (bit i, null = all valid), i < min(*d_count, max_n)
+hipError_t launch_aggregate_arrays(const int64_t* x, const uint64_t* valid, const uint64_t* d_count, uint64_t max_n,
+                                   uint32_t ops, int type, int64_t* workspace, int64_t* out, hipStream_t stream);
 // after a merge: every 64-row word holding one of the m merged rows (ascending) sliced again from
 // the column as it stands
 hipError_t launch_bitslice_reslice(const int64_t* rows, uint64_t m, const void* col, int type, const uint64_t* validity,

@@ -2187,6 +2187,281 @@ __global__ __launch_bounds__(256) void bitslice_compare_kernel(SliceSet sl, uint
     }
 }
 
+// Aggregate: SUM / MIN / MAX / COUNT of the column over the rows a program keeps, from the slices
+// alone (O'Neil & Quass 1997 §3; Rinfret et al. 2001). Fused evaluate + aggregate in the eval_*
+// family: persistent workgroups walk tiles of one zone (load_tile / eval_words / tail_mask, live-tile
+// lists, every program form; K = 0: every row below n_rows), F stays in registers and no bitvector
+// is written. Per pair of words Fv = F ∧ valid, then the slices are streamed once from the top
+// down in chunks of up to 8 loaded before use (16-byte non-temporal loads, as ripple_chunk):
+//   SUM     per chunk Σ_j popc(Fv ∧ w_j)·2^j is at most 2^15, shifted to the chunk's lowest slice
+//           and added to the thread's 128-bit running sum Σ_s 2^s·c_s — exact at any partition size
+//           (the whole sum stays below 2^64 · rows);
+//   MIN/MAX the candidate ripple per word, cand = (cand ∧ ¬w) if that is non-empty (bit 0) else cand
+//           (bit 1), MAX mirrored, with selects; the word's offset is built a bit per slice and
+//           reduced unsigned per thread, wave, workgroup. A word with Fv = 0 yields 2^b - 1 / 0,
+//           which can win only when no row qualifies.
+// A pair whose Fv is zero across the whole wave skips its slice loads (a wave-uniform branch).
+// Traffic: (b + K [+ 1 with validity])·n/8 bytes read over the live zones, nothing written.
+template <bool SUM, bool MINMAX, int CNT>
+__device__ __forceinline__ void agg_chunk(const SliceSet& sl, int top, uint64_t pi, const u64x2& f, U128& acc,
+                                          u64x2& cmin, u64x2& cmax, u64x2& omin, u64x2& omax) {
+    u64x2 w[CNT];
+#pragma unroll
+    for (int j = 0; j < CNT; ++j) w[j] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(sl.s[top - j]) + pi);
+    if (SUM) {
+        uint32_t local = 0;  // Horner from the chunk's top slice: ≤ 128·(2^CNT - 1)
+#pragma unroll
+        for (int j = 0; j < CNT; ++j) local = (local << 1) + (uint32_t)(__popcll(f.x & w[j].x) + __popcll(f.y & w[j].y));
+        acc = u128_add(acc, u128_shl(local, (uint32_t)(top - CNT + 1)));
+    }
+    if (MINMAX) {
+#pragma unroll
+        for (int j = 0; j < CNT; ++j) {
+            const u64x2 tn = cmin & ~w[j], tx = cmax & w[j];
+            const bool nx = tn.x != 0, ny = tn.y != 0, xx = tx.x != 0, xy = tx.y != 0;
+            cmin.x = nx ? tn.x : cmin.x;
+            cmin.y = ny ? tn.y : cmin.y;
+            cmax.x = xx ? tx.x : cmax.x;
+            cmax.y = xy ? tx.y : cmax.y;
+            omin.x = (omin.x << 1) | (nx ? 0ull : 1ull);
+            omin.y = (omin.y << 1) | (ny ? 0ull : 1ull);
+            omax.x = (omax.x << 1) | (xx ? 1ull : 0ull);
+            omax.y = (omax.y << 1) | (xy ? 1ull : 0ull);
+        }
+    }
+}
+
+template <int K, int FORM, bool SUM, bool MINMAX>
+__global__ __launch_bounds__(512, 4) void eval_slice_aggregate(EvalArgs a, SliceAggArgs g) {
+    constexpr int THREADS = 512, PAIRS = 2, NW = 4;
+    constexpr uint64_t TILE_WORDS = (uint64_t)THREADS * NW;
+    static_assert(TILE_WORDS == kAggTileWords, "a tile is one zone");
+    constexpr int NWAVES = THREADS / 64;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    uint64_t c_rows = 0, c_valid = 0;
+    U128 acc{0, 0};
+    uint64_t mn = ~0ull, mx = 0;
+    const uint32_t n_idx = a.num_tiles;
+    for (uint32_t i = blockIdx.x; i < n_idx; i += gridDim.x) {
+        const uint64_t tile_word0 = (uint64_t)tile_at(a, i) * TILE_WORDS;
+        uint64_t r[NW];
+        if constexpr (K > 0) {
+            u64x2 v[K][PAIRS];
+            load_tile<K, PAIRS, THREADS>(a, tile_word0, t, v);
+            eval_words<K, NW, FORM>(a.prog, v, r);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) r[j] = ~0ull;
+        }
+        tail_mask<NW, THREADS>(a, tile_word0, t, r);
+        u64x2 fv[PAIRS];
+#pragma unroll
+        for (int p = 0; p < PAIRS; ++p) {
+            fv[p].x = r[2 * p];
+            fv[p].y = r[2 * p + 1];
+        }
+        if (g.validity) {
+            if (tile_word0 + TILE_WORDS <= a.n_words) {  // uniform: the whole tile lies below the last word
+#pragma unroll
+                for (int p = 0; p < PAIRS; ++p)
+                    fv[p] &= reinterpret_cast<const u64x2*>(g.validity + tile_word0)[p * THREADS + t];
+            } else {  // the tile holding the last word: nothing at or past n_words is read
+#pragma unroll
+                for (int p = 0; p < PAIRS; ++p) {
+                    const uint64_t gw = word_index<THREADS>(tile_word0, 2 * p, t);
+                    fv[p].x &= gw < a.n_words ? g.validity[gw] : 0ull;
+                    fv[p].y &= gw + 1 < a.n_words ? g.validity[gw + 1] : 0ull;
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < PAIRS; ++p) {
+            c_rows += (uint64_t)(__popcll(r[2 * p]) + __popcll(r[2 * p + 1]));
+            c_valid += (uint64_t)(__popcll(fv[p].x) + __popcll(fv[p].y));
+        }
+        if (!SUM && !MINMAX) continue;
+#pragma unroll
+        for (int p = 0; p < PAIRS; ++p) {
+            const u64x2 f = fv[p];
+            if (__ballot((f.x | f.y) != 0) == 0) continue;  // no qualifying row in the wave's 128 words
+            const uint64_t pi = (tile_word0 >> 1) + (uint64_t)(p * THREADS + t);
+            u64x2 cmin = f, cmax = f, omin = {0ull, 0ull}, omax = {0ull, 0ull};
+            int top = (int)g.n_slices - 1;
+            switch (g.n_slices & 7u) {  // the top slices that fill no chunk of 8, then whole chunks
+            case 1: agg_chunk<SUM, MINMAX, 1>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
+            case 2: agg_chunk<SUM, MINMAX, 2>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
+            case 3: agg_chunk<SUM, MINMAX, 3>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
+            case 4: agg_chunk<SUM, MINMAX, 4>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
+            case 5: agg_chunk<SUM, MINMAX, 5>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
+            case 6: agg_chunk<SUM, MINMAX, 6>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
+            case 7: agg_chunk<SUM, MINMAX, 7>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
+            default: break;
+            }
+            top -= (int)(g.n_slices & 7u);
+            for (; top >= 7; top -= 8) agg_chunk<SUM, MINMAX, 8>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax);
+            if (MINMAX) {
+                // (a word of the pair without a qualifying row gives 2^b - 1 / 0: never below / above
+                // the other word's offset)
+                const uint64_t lo = omin.x < omin.y ? omin.x : omin.y, hi = omax.x > omax.y ? omax.x : omax.y;
+                mn = lo < mn ? lo : mn;
+                mx = hi > mx ? hi : mx;
+            }
+        }
+    }
+    // wave, then workgroup: exact integer adds and unsigned min / max, so any order gives the same
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        U128 o;
+        o.lo = __shfl_xor(acc.lo, d, 64);
+        o.hi = __shfl_xor(acc.hi, d, 64);
+        acc = u128_add(acc, o);
+        const uint64_t omn = __shfl_xor(mn, d, 64), omx = __shfl_xor(mx, d, 64);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+        c_rows += __shfl_xor(c_rows, d, 64);
+        c_valid += __shfl_xor(c_valid, d, 64);
+    }
+    __shared__ uint64_t s_part[NWAVES][6];
+    if (lane == 0) {
+        s_part[wave][0] = acc.lo;
+        s_part[wave][1] = acc.hi;
+        s_part[wave][2] = mn;
+        s_part[wave][3] = mx;
+        s_part[wave][4] = c_valid;
+        s_part[wave][5] = c_rows;
+    }
+    __syncthreads();
+    if (t == 0) {
+        U128 s{0, 0};
+        uint64_t lo = ~0ull, hi = 0, cv = 0, cr = 0;
+        for (int w = 0; w < NWAVES; ++w) {
+            s = u128_add(s, U128{s_part[w][0], s_part[w][1]});
+            lo = s_part[w][2] < lo ? s_part[w][2] : lo;
+            hi = s_part[w][3] > hi ? s_part[w][3] : hi;
+            cv += s_part[w][4];
+            cr += s_part[w][5];
+        }
+        int64_t* part = g.workspace + (uint64_t)kAggPartial * blockIdx.x;
+        part[0] = (int64_t)s.lo;
+        part[1] = (int64_t)s.hi;
+        part[2] = (int64_t)lo;
+        part[3] = (int64_t)hi;
+        part[4] = (int64_t)cv;
+        finish_ticket(a.ticket, a.count, cr);
+    }
+}
+
+// The column path's reduction: x[i] = the probed value of qualifying row i as the ABI carries it
+// (FLOAT / DOUBLE patterns, UINT64 bits; 0 at NULL rows), valid bit i its NULL-ness. The sum adds
+// the values (UINT64 unsigned, every other type signed) in 128 bits; min / max go through the
+// comparison key, kept as the unsigned-ordered key ^ 2^63 — an offset from base INT64_MIN, so the
+// finishing wave maps them as it maps the slices' offsets.
+__global__ __launch_bounds__(256) void aggregate_arrays_kernel(const int64_t* __restrict__ x,
+                                                               const uint64_t* __restrict__ valid,
+                                                               const uint64_t* __restrict__ d_count, uint64_t max_n,
+                                                               uint32_t ops, int type, int64_t* __restrict__ workspace) {
+    const uint64_t n = min(*d_count, max_n);
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    U128 acc{0, 0};
+    uint64_t mn = ~0ull, mx = 0, cv = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (valid && !((valid[i >> 6] >> (i & 63)) & 1ull)) continue;
+        const int64_t v = x[i];
+        ++cv;
+        if (ops & kAggSum) acc = u128_add(acc, U128{(uint64_t)v, type == kTypeUInt64 || v >= 0 ? 0ull : ~0ull});
+        const uint64_t off = (uint64_t)value_key(type, v) ^ 0x8000000000000000ull;
+        mn = off < mn ? off : mn;
+        mx = off > mx ? off : mx;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        U128 o;
+        o.lo = __shfl_xor(acc.lo, d, 64);
+        o.hi = __shfl_xor(acc.hi, d, 64);
+        acc = u128_add(acc, o);
+        const uint64_t omn = __shfl_xor(mn, d, 64), omx = __shfl_xor(mx, d, 64);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+        cv += __shfl_xor(cv, d, 64);
+    }
+    __shared__ uint64_t s_part[4][5];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        s_part[wave][0] = acc.lo;
+        s_part[wave][1] = acc.hi;
+        s_part[wave][2] = mn;
+        s_part[wave][3] = mx;
+        s_part[wave][4] = cv;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        U128 s{0, 0};
+        uint64_t lo = ~0ull, hi = 0, c = 0;
+        for (int w = 0; w < 4; ++w) {
+            s = u128_add(s, U128{s_part[w][0], s_part[w][1]});
+            lo = s_part[w][2] < lo ? s_part[w][2] : lo;
+            hi = s_part[w][3] > hi ? s_part[w][3] : hi;
+            c += s_part[w][4];
+        }
+        int64_t* part = workspace + (uint64_t)kAggPartial * blockIdx.x;
+        part[0] = (int64_t)s.lo;
+        part[1] = (int64_t)s.hi;
+        part[2] = (int64_t)lo;
+        part[3] = (int64_t)hi;
+        part[4] = (int64_t)c;
+        // count_rows for the finishing wave (a scan that counted into the slot itself left it there)
+        if (blockIdx.x == 0 && d_count != agg_count_slot(workspace)) *agg_count_slot(workspace) = n;
+    }
+}
+
+// One wave combines the workgroups' partials (beside sum_partials_kernel: a strided share per lane,
+// then a butterfly) and writes the six result slots. from_slices: the partial sums are Σ 2^s·c_s and
+// the offsets count from `base` (slice_agg_combine); else the sums are the values' and the offsets
+// count from INT64_MIN.
+__global__ __launch_bounds__(64) void aggregate_finish_kernel(const int64_t* __restrict__ workspace, int nblocks,
+                                                              uint32_t ops, int type, int64_t base, int from_slices,
+                                                              int64_t* __restrict__ out) {
+    const int lane = threadIdx.x;
+    U128 acc{0, 0};
+    uint64_t mn = ~0ull, mx = 0, cv = 0;
+    for (int b = lane; b < nblocks; b += 64) {
+        const int64_t* part = workspace + (uint64_t)kAggPartial * b;
+        acc = u128_add(acc, U128{(uint64_t)part[0], (uint64_t)part[1]});
+        mn = (uint64_t)part[2] < mn ? (uint64_t)part[2] : mn;
+        mx = (uint64_t)part[3] > mx ? (uint64_t)part[3] : mx;
+        cv += (uint64_t)part[4];
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        U128 o;
+        o.lo = __shfl_xor(acc.lo, d, 64);
+        o.hi = __shfl_xor(acc.hi, d, 64);
+        acc = u128_add(acc, o);
+        const uint64_t omn = __shfl_xor(mn, d, 64), omx = __shfl_xor(mx, d, 64);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+        cv += __shfl_xor(cv, d, 64);
+    }
+    if (lane == 0) {
+        int64_t r[4];
+        if (from_slices) {
+            slice_agg_combine(type, base, cv, acc, mn, mx, ops, r);
+        } else {
+            slice_agg_combine(type, INT64_MIN, cv, U128{0, 0}, mn, mx, ops & ~kAggSum, r);
+            if (ops & kAggSum) {
+                r[0] = (int64_t)acc.lo;
+                r[1] = (int64_t)acc.hi;
+            }
+        }
+        out[0] = r[0];
+        out[1] = r[1];
+        out[2] = r[2];
+        out[3] = r[3];
+        out[4] = (int64_t)cv;
+        out[5] = (int64_t)workspace[(uint64_t)kAggPartial * kAggMaxGrid];
+    }
+}
+
 // ------------------------------------------------------------------ index build: column stats
 
 // min / max / any-valid of a column (the statistics an index build needs; the reference
@@ -3896,6 +4171,51 @@ hipError_t launch_bitslice_compare(const SliceSet& slices, uint32_t n_slices, co
     else if (need_hi) CUBIT_SLICED(false, true);
     else CUBIT_SLICED(false, false);
 #undef CUBIT_SLICED
+    return hipGetLastError();
+}
+
+// SUM-only, MIN/MAX-only and both are kernels of their own (the ops are resolved outside the slice
+// loop: a SUM pays no ripple, a MIN / MAX no popcounts); a call for the counts alone runs the SUM form
+template <int K, int FORM>
+void launch_slice_aggregate_kf(const EvalArgs& a, const SliceAggArgs& g, uint32_t ops, unsigned grid, hipStream_t s,
+                               hipEvent_t e0, hipEvent_t e1) {
+    const bool minmax = (ops & (kAggMin | kAggMax)) != 0;
+    if (!minmax)
+        hipExtLaunchKernelGGL((eval_slice_aggregate<K, FORM, true, false>), dim3(grid), dim3(512), 0, s, e0, e1, 0, a, g);
+    else if (ops & kAggSum)
+        hipExtLaunchKernelGGL((eval_slice_aggregate<K, FORM, true, true>), dim3(grid), dim3(512), 0, s, e0, e1, 0, a, g);
+    else
+        hipExtLaunchKernelGGL((eval_slice_aggregate<K, FORM, false, true>), dim3(grid), dim3(512), 0, s, e0, e1, 0, a, g);
+}
+
+hipError_t launch_eval_slice_aggregate(EvalArgs a, const SliceAggArgs& g, uint32_t ops, int type, int64_t base,
+                                       int n_cus, int64_t* out, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+    if (g.n_slices > kMaxSlices || a.num_tiles == 0 || !g.workspace || !a.ticket) return hipErrorInvalidValue;
+    a.count = agg_count_slot(g.workspace);
+    // persistent grid: two 512-thread workgroups per CU, as the fused sum's
+    const unsigned grid =
+        std::max(1u, std::min<unsigned>(a.num_tiles, std::min<unsigned>(2u * (unsigned)n_cus, kAggMaxGrid)));
+    hipError_t e = hipSuccess;
+    if (a.prog.n_leaves == 0)
+        launch_slice_aggregate_kf<0, FORM_CONJ>(a, g, ops, grid, stream, ev0, ev1);
+    else
+        e = dispatch_k_form(a.prog, [&](auto k, auto form) {
+            launch_slice_aggregate_kf<k.value, form.value>(a, g, ops, grid, stream, ev0, ev1);
+        });
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(aggregate_finish_kernel, dim3(1), dim3(64), 0, stream, g.workspace, (int)grid, ops, type, base, 1,
+                       out);
+    return hipGetLastError();
+}
+
+hipError_t launch_aggregate_arrays(const int64_t* x, const uint64_t* valid, const uint64_t* d_count, uint64_t max_n,
+                                   uint32_t ops, int type, int64_t* workspace, int64_t* out, hipStream_t stream) {
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((max_n + 2047) / 2048, kAggMaxGrid));
+    hipLaunchKernelGGL(aggregate_arrays_kernel, dim3(grid), dim3(256), 0, stream, x, valid, d_count, max_n, ops, type,
+                       workspace);
+    hipLaunchKernelGGL(aggregate_finish_kernel, dim3(1), dim3(64), 0, stream, workspace, (int)grid, ops, type,
+                       (int64_t)0, 0, out);
     return hipGetLastError();
 }
 

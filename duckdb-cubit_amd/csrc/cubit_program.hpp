@@ -128,6 +128,98 @@ inline SlicedInterval sliced_interval(int cmp_or_between, int64_t c, int64_t c2,
     return s;
 }
 
+// ---- aggregates from a bit-sliced index (O'Neil & Quass 1997 §3; Rinfret et al. 2001)
+//
+// With F the filter's rows, v the column's validity and c_s = popcount(F ∧ v ∧ slice s),
+// SUM = count(F ∧ v)·base + Σ_s 2^s·c_s, and MIN / MAX are base plus the smallest / largest offset.
+// The combine step below runs on the device (the finishing kernel, cubit_kernels.hip) and on the
+// CPU (tests/slice_agg_core.cpp): every operation is unsigned and modular, so base = INT64_MIN with
+// 64 slices overflows nothing signed. Type codes as CUBIT_TYPE_*.
+#ifdef __HIPCC__
+#define CUBIT_HD __host__ __device__
+#else
+#define CUBIT_HD
+#endif
+
+struct U128 {
+    uint64_t lo, hi;
+};
+CUBIT_HD inline U128 u128_add(U128 a, U128 b) {
+    const uint64_t lo = a.lo + b.lo;
+    return {lo, a.hi + b.hi + (lo < a.lo ? 1u : 0u)};
+}
+// x·2^s mod 2^128, s < 64
+CUBIT_HD inline U128 u128_shl(uint64_t x, uint32_t s) { return {x << s, s ? x >> (64 - s) : 0}; }
+// a·b as 128 bits, both unsigned
+CUBIT_HD inline U128 u128_mul(uint64_t a, uint64_t b) {
+    const unsigned __int128 p = (unsigned __int128)a * b;
+    return {(uint64_t)p, (uint64_t)(p >> 64)};
+}
+// Σ_s 2^s·counts[s] over the first n_slices (≤ 64) per-slice counts
+CUBIT_HD inline U128 slice_weighted_sum(const uint64_t* counts, uint32_t n_slices) {
+    U128 w{0, 0};
+    for (uint32_t s = 0; s < n_slices && s < 64; ++s) w = u128_add(w, u128_shl(counts[s], s));
+    return w;
+}
+// a comparison key as cubit_table_column_statistics hands it out (cubit_fp_value, restated so the
+// device can call it): FLOAT / DOUBLE keys → bit patterns, UINT64 keys → the value's bits
+CUBIT_HD inline int64_t agg_key_value(int type, int64_t key) {
+    if (type == CUBIT_TYPE_UINT64) return (int64_t)((uint64_t)key ^ 0x8000000000000000ull);
+    if (type == CUBIT_TYPE_FLOAT) return key < 0 ? (int64_t)(0x80000000u | (uint32_t)(0 - (uint64_t)key)) : key;
+    if (type == CUBIT_TYPE_DOUBLE) return key < 0 ? (int64_t)(0x8000000000000000ull | (0 - (uint64_t)key)) : key;
+    return key;
+}
+constexpr uint32_t kAggSum = 1u, kAggMin = 2u, kAggMax = 4u;  // CUBIT_AGG_SUM / _MIN / _MAX
+// The aggregate's first four result slots {sum_lo, sum_hi, min, max} (slots of ops not asked for: 0).
+// `weighted` = Σ_s 2^s·c_s, count_valid = count(F ∧ v), min_off / max_off = the smallest / largest
+// offset among those rows (anything when there is none), base = the slices' base key. The values of a
+// UINT64 column are (key ^ 2^63) = (base ^ 2^63) + offset, summed unsigned; every other type's value
+// is its key, summed signed: count·base in two's complement is the unsigned product less count·2^64
+// when base is negative.
+CUBIT_HD inline void slice_agg_combine(int type, int64_t base, uint64_t count_valid, U128 weighted, uint64_t min_off,
+                                       uint64_t max_off, uint32_t ops, int64_t out[4]) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (ops & kAggSum) {
+        const bool uns = type == CUBIT_TYPE_UINT64;
+        const uint64_t b = uns ? (uint64_t)base ^ 0x8000000000000000ull : (uint64_t)base;
+        U128 s = u128_mul(count_valid, b);
+        if (!uns && base < 0) s.hi -= count_valid;
+        s = u128_add(s, weighted);
+        out[0] = (int64_t)s.lo;
+        out[1] = (int64_t)s.hi;
+    }
+    if (ops & kAggMin) out[2] = agg_key_value(type, (int64_t)((uint64_t)base + min_off));
+    if (ops & kAggMax) out[3] = agg_key_value(type, (int64_t)((uint64_t)base + max_off));
+}
+// the same from the 64 per-slice counts (counts past the index's slices are 0)
+CUBIT_HD inline void slice_agg_combine(int type, int64_t base, uint64_t count_valid, const uint64_t counts[64],
+                                       uint64_t min_off, uint64_t max_off, uint32_t ops, int64_t out[4]) {
+    slice_agg_combine(type, base, count_valid, slice_weighted_sum(counts, 64), min_off, max_off, ops, out);
+}
+
+// Which path cubit_table_aggregate takes: the slices (true) or scan + probe + reduce over the column.
+// force_slices / force_column: CUBIT_AGG_FROM_SLICES / _FROM_COLUMN (the caller has refused both
+// together, and FROM_SLICES without a usable index). Otherwise the path that moves fewer bytes:
+//   slices: every live row reads its bit of the b slices, the K program leaves and, when the column
+//           is nullable, its validity: (b + K + nullable)/8 bytes per live row;
+//   column: the scan reads K/8 bytes per live row; per estimated qualifying row the id is written and
+//           read (16 bytes), the probed value and its validity are written and read (16 bytes) and
+//           the gather moves one 128-byte line, but never more lines than the column has.
+// The constants are derived from bytes alone and stay so: at 612 M rows the measured crossover
+// (scripts/slice_agg_timing.py, interpolated between its 1e-3 and 2 % points: about 0.9 % of the rows
+// for 12 slices, 1.6 % for 24) lies where this rule puts it (0.94 %, 1.9 %), DESIGN.md §3.
+// Correctness never depends on the choice.
+inline bool aggregate_from_slices(bool force_slices, bool force_column, bool usable, uint32_t bits, uint32_t k_leaves,
+                                  bool nullable, uint64_t live_rows, uint64_t rows, uint64_t est_rows,
+                                  uint64_t elem_bytes) {
+    if (force_column || !usable) return false;
+    if (force_slices) return true;
+    const double slices = (double)(bits + k_leaves + (nullable ? 1u : 0u)) / 8.0 * (double)live_rows;
+    const double gathered = std::min(128.0 * (double)est_rows, (double)elem_bytes * (double)rows);
+    const double column = (double)k_leaves / 8.0 * (double)live_rows + 32.0 * (double)est_rows + gathered;
+    return slices <= column;
+}
+
 // One past the last node of the subtree rooted at node i of a prefix-order node array, or -1 when
 // the array ends inside it. A negative child count reads as none.
 inline int filter_subtree_end(const cubit_filter_node* nodes, uint32_t n_nodes, uint32_t i) {

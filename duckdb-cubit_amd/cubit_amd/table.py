@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import weakref
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -223,6 +223,16 @@ class Dictionary:
             self.close()
         except Exception:
             pass
+
+
+class Aggregate(NamedTuple):
+    """CubitTable.aggregate's result."""
+
+    sum: int
+    min: Optional[int]
+    max: Optional[int]
+    count_valid: int
+    count_rows: int
 
 
 class CubitTable:
@@ -602,6 +612,48 @@ class CubitTable:
         out.free()
         cnt.free()
         return (hi << 64) + (lo & (2 ** 64 - 1)), n
+
+    def aggregate(self, col: int, filter_set: Optional[TableFilterSet] = None, residual: Optional[Residual] = None,
+                  txn: Optional[L.Txn] = None, ops: Optional[int] = None, path: Optional[str] = None,
+                  zonemap: bool = True) -> "Aggregate":
+        """SELECT sum(col), min(col), max(col), count(col), count(*) WHERE <filter> →
+        Aggregate(sum, min, max, count_valid, count_rows). ops: L.AGG_SUM | L.AGG_MIN | L.AGG_MAX
+        (None: every one the column's type has — SUM is refused on FLOAT / DOUBLE / dictionary
+        columns). sum is a Python int, signed, or unsigned for a UINT64 column (0 when not asked for
+        or over no row); min / max are in column_statistics' form, None when not asked for or when
+        no qualifying row is valid (count_valid == 0). path: None lets the library choose, "slices"
+        forces the column's bit-sliced index, "column" the scan + probe + reduce."""
+        type_ = self.types.get(col)
+        no_sum = type_ in (L.TYPE_FLOAT, L.TYPE_DOUBLE, L.TYPE_VARCHAR) or col in self.huge
+        if ops is None:
+            ops = L.AGG_ALL & ~(L.AGG_SUM if no_sum else 0)
+        if path not in (None, "slices", "column"):
+            raise ValueError(f"path {path!r}")
+        flags = int(ops) | {None: 0, "slices": L.AGG_FROM_SLICES, "column": L.AGG_FROM_COLUMN}[path]
+        flags |= 0 if zonemap else L.AGG_NO_ZONEMAP
+        plan = serialize(filter_set, residual)
+        arr = to_ctypes(plan.nodes)
+        out = self.ctx.alloc(48)
+        try:
+            L.check(self.lib.cubit_table_aggregate(self.handle, arr, len(plan.nodes),
+                                                   C.byref(txn) if txn is not None else None, col, flags,
+                                                   C.c_void_p(out.addr)))
+            self.ctx.check()
+            lo, hi, mn, mx, cv, cr = (int(x) for x in out.download(np.int64, 6))
+        finally:
+            out.free()
+        total = ((hi << 64) + (lo & (2 ** 64 - 1)))
+        if type_ == L.TYPE_UINT64:
+            total &= 2 ** 128 - 1
+        some = cv > 0
+        return Aggregate(total, mn if (ops & L.AGG_MIN) and some else None, mx if (ops & L.AGG_MAX) and some else None,
+                         cv, cr)
+
+    def last_aggregate_from_slices(self) -> bool:
+        """Whether the last aggregate() read the column's bit slices (else the column itself)."""
+        v = C.c_int()
+        L.check(self.lib.cubit_table_last_aggregate(self.handle, C.byref(v)))
+        return bool(v.value)
 
     def last_sum_packed(self) -> bool:
         v = C.c_int()

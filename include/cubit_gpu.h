@@ -507,7 +507,9 @@ int cubit_table_last_packed(cubit_table *t, uint32_t *n_leaves);
  * candidate checks, equality unions, bins and narrowed (masked) compares stay as they are. On a
  * column whose only index is bit-sliced, the constant bounds of a conjunction (a <= x AND x < b)
  * fold into one leaf, one pass over the slices. On by default; results are identical either way.
- * cubit_table_last_sliced: leaves the last scan / sum_product built from slices. */
+ * cubit_table_last_sliced: leaves the last scan / sum_product / aggregate built from slices, plus
+ * one when the aggregate itself read its column's slices (cubit_table_aggregate). Off, it also
+ * sends cubit_table_aggregate to the column path. */
 int cubit_table_use_sliced(cubit_table *t, int on);
 int cubit_table_last_sliced(cubit_table *t, uint32_t *n_leaves);
 /* Selection narrowing (on by default): in a conjunction, a constant comparison on a column the
@@ -724,6 +726,58 @@ int cubit_table_sum_product(cubit_table *t, const cubit_filter_node *nodes, uint
 int cubit_table_last_sum_decode(cubit_table *t, uint32_t *n_values);
 /* Whether the last sum_product read a from its BITPACKING segments. */
 int cubit_table_last_sum_packed(cubit_table *t, int *packed);
+
+/* SELECT sum(col), min(col), max(col), count(col), count(*) WHERE <filter> of one column, ready on
+ * the context's stream with no host round trip. d_out (device, 6 int64) =
+ * {sum_lo, sum_hi, min, max, count_valid, count_rows}; ops = CUBIT_AGG_SUM | _MIN | _MAX names the
+ * aggregates wanted, the two counts are always written and the slots of ops not asked for are 0.
+ *   The aggregates run over the qualifying rows where col is not NULL: SUM, MIN and MAX ignore NULLs
+ * (the reference's BaseSumOperation and MinMaxBase answer IgnoreNull() true,
+ * src/include/duckdb/core_functions/aggregate/sum_helpers.hpp:170,
+ * src/core_functions/aggregate/distributive/minmax.cpp:84, so AggregateExecutor::UnaryFlatLoop skips
+ * the rows its validity mask clears, common/vector_operations/aggregate_executor.hpp:53-90),
+ * count_valid is COUNT(col) (CountFunction::CountFlatLoop counts the valid rows only,
+ * src/function/aggregate/distributive/count.cpp:60-106) and count_rows is COUNT(*) (CountStarFunction,
+ * count.cpp:25). With count_valid = 0 the reference's SUM / MIN / MAX are NULL: sum is 0 and
+ * min / max are unspecified here, SQL NULL is the caller's to emit.
+ *   sum is the exact 128-bit two's-complement sum of the values (a UINT64 column's values are summed
+ * unsigned); min / max are in the form cubit_table_column_statistics reports them (FLOAT / DOUBLE bit
+ * patterns: the key order is DuckDB's value order, NaN above +inf, -0.0 = +0.0 reported as +0.0;
+ * UINT64 bits; a dictionary column's codes). An empty partition, or a filter that folds to FALSE,
+ * gives zero counts.
+ *   CUBIT_ERR_UNSUPPORTED: SUM on a FLOAT / DOUBLE / VARCHAR / dictionary column (its keys are not
+ * linear in the value; MIN / MAX on them work). CUBIT_ERR_INVALID: an unregistered column, ops or
+ * flags outside the bits below, both force flags together.
+ *   Two paths give the same result. From the slices: with a non-empty bit-sliced index
+ * (CUBIT_INDEX_SLICED) on col, cubit_table_use_sliced on and no update record of col visible to
+ * txn, one fused kernel evaluates the filter program (visibility and zonemap skip included) and
+ * aggregates from the slices: SUM = count_valid * base + sum over s of 2^s * popcount(F AND valid AND
+ * slice s), MIN / MAX a ripple from the top slice down (O'Neil & Quass 1997), (b + K [+ 1]) / 8 bytes
+ * per row of the evaluated zones. From the column: scan into scratch, probe with validity (visible
+ * MVCC updates applied), reduce. Without a force flag the path estimated to move fewer bytes is
+ * taken. CUBIT_AGG_FROM_SLICES forces the first (CUBIT_ERR_INVALID when the conditions above do
+ * not hold), CUBIT_AGG_FROM_COLUMN the second; cubit_table_last_aggregate tells which ran
+ * (cubit_table_last_sliced counts the slice path as one more sliced leaf; cubit_table_last_zones
+ * reports the evaluated zones). */
+#define CUBIT_AGG_SUM 1u
+#define CUBIT_AGG_MIN 2u
+#define CUBIT_AGG_MAX 4u            /* the two counts are always written */
+#define CUBIT_AGG_FROM_SLICES 16u   /* force the slice path (CUBIT_ERR_INVALID if the column has no usable bit-sliced index) */
+#define CUBIT_AGG_FROM_COLUMN 32u   /* force the column path */
+#define CUBIT_AGG_NO_ZONEMAP 64u    /* as CUBIT_SCAN_NO_ZONEMAP */
+int cubit_table_aggregate(cubit_table *t, const cubit_filter_node *nodes, uint32_t n_nodes, const cubit_txn *txn,
+                          int col, uint32_t ops, int64_t *d_out);
+int cubit_table_last_aggregate(cubit_table *t, int *from_slices);
+/* The slice path's kernel on a caller's slices, as cubit_bitslice_compare is the compare's: d_slices
+ * as there (n_slices 0 ... 64 device pointers, each cubit_padded_words(n_rows) words, 16-byte
+ * aligned), d_validity NULL = every row valid, read only below ceil(n_rows / 64) words; d_filter =
+ * the qualifying rows as a bitvector of cubit_padded_words(n_rows) words (bits at or past n_rows are
+ * ignored), NULL = every row below n_rows. type / base: the column's type (CUBIT_TYPE_INT32, _INT64,
+ * _UINT64, _FLOAT, _DOUBLE, _VARCHAR; SUM refused as above) and the slices' base key; ops = CUBIT_AGG_SUM |
+ * _MIN | _MAX. d_out as cubit_table_aggregate's. */
+int cubit_bitslice_aggregate(cubit_ctx *ctx, const uint64_t *const *d_slices, uint32_t n_slices,
+                             const uint64_t *d_validity, const uint64_t *d_filter, uint64_t n_rows,
+                             int type, int64_t base, uint32_t ops, int64_t *d_out);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,146 @@
+"""Time cubit_table_aggregate at the bench's scale (612 M rows, one process) on both forced paths —
+from the column's bit slices, and scan + probe + reduce over the column — for a 12-bit INT32 column
+and a 24-bit INT64 column, at selectivities 1e-6 / 1e-3 / 2 % / 50 % / 100 % (a filter column with a
+RANGE index whose keys are the filter constants, so the program is one index leaf and no K0 pass runs
+inside the timed calls), SUM alone and SUM + MIN + MAX. Beside them, in the same run and over the
+same number of slices, one cubit_bitslice_compare pass as the byte-rate yardstick: it reads the
+same b slices and writes one bitvector where the aggregate reads one leaf.
+  Call time: three rounds, each timing five back-to-back calls between two synchronisations, the
+kernels alternated inside a round so drift hits them alike; the spread is the range over the rounds.
+Kernel time: the dispatch-stamped time of the fused kernel and of the compare kernel (context timing),
+five launches each. Every rate is the bytes the kernel has to move over its time. The two paths'
+six result words are compared before anything is timed; a difference ends the run."""
+import ctypes as C
+import os
+import sys
+import time
+
+import numpy as np
+
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "duckdb-cubit_amd"))
+from cubit_amd import _lib as L  # noqa: E402
+from cubit_amd import filters as F  # noqa: E402
+from cubit_amd.table import Context, CubitTable, DeviceBuffer  # noqa: E402
+
+n = int(args[0]) if args else 612_000_000
+ROUNDS, LAUNCHES = 3, 5
+F_SPAN = 1_000_000
+SELS = [("1e-6", 1), ("1e-3", 1_000), ("2 %", 20_000), ("50 %", 500_000), ("100 %", None)]
+OPS = [("SUM", L.AGG_SUM), ("SUM+MIN+MAX", L.AGG_ALL)]
+rng = np.random.default_rng(9)
+print(f"{n} rows; {ROUNDS} rounds of {LAUNCHES} calls per kernel", flush=True)
+
+ctx = Context(0)
+lib = L.gpu_lib()
+pw = int(lib.cubit_padded_words(n))
+t = CubitTable(ctx, n)
+f = rng.integers(0, F_SPAN, n, dtype=np.int32)
+t.add_column(0, f)
+t.build_index(0, L.INDEX_RANGE, [c for _, c in SELS if c is not None])
+del f
+COLS = [(1, "INT32, 2,526-value span", rng.integers(8035, 8035 + 2526, n, dtype=np.int32), 8035, 8035 + 2525),
+        (2, "INT64, 2^24 span", rng.integers(0, 2 ** 24, n, dtype=np.int64), 0, 2 ** 24 - 1)]
+out_s, out_c = DeviceBuffer(ctx, 64), DeviceBuffer(ctx, 64)
+words = DeviceBuffer(ctx, pw * 8)
+
+
+def timed(launch):
+    launch()
+    ctx.sync()
+    t0 = time.perf_counter()
+    for _ in range(LAUNCHES):
+        launch()
+    ctx.sync()
+    return (time.perf_counter() - t0) * 1e3 / LAUNCHES
+
+
+def kernel_ms(launch):
+    """Mean dispatch-stamped time of the last timed launch of each call (the fused kernel / the compare)."""
+    ctx.enable_timing(True)
+    launch()
+    ctx.sync()
+    ctx.timing_reset()
+    for _ in range(LAUNCHES):
+        launch()
+    ctx.sync()
+    ms = ctx.kernel_times_ms()
+    ctx.enable_timing(False)
+    per_call = len(ms) // LAUNCHES
+    assert per_call >= 1 and len(ms) == LAUNCHES * per_call, len(ms)
+    return sum(ms[per_call - 1::per_call]) / LAUNCHES
+
+
+def line(what, ms, moved=None):
+    rate = f" = {moved / 1e9:.2f} GB at {moved / min(ms) / 1e9:.2f} TB/s" if moved else ""
+    print(f"{what}: {' / '.join(f'{x:.3f}' for x in ms)} ms (spread {max(ms) - min(ms):.3f}); best {min(ms):.3f} ms{rate}",
+          flush=True)
+
+
+for col, name, v, base, top in COLS:
+    elem = v.dtype.itemsize
+    bits = int(top - base).bit_length()
+    t.add_column(col, v)
+    del v
+    t.build_index(col, L.INDEX_SLICED)
+    assert t.index_info(col)[0] == bits
+    # the yardstick's own slices, built from the table's column on the device
+    d_col, typ = t.column_data(col)
+    slices = DeviceBuffer(ctx, bits * pw * 8)
+    ptrs = (C.c_void_p * bits)(*[slices.addr + s * pw * 8 for s in range(bits)])
+    L.check(lib.cubit_bitslice_build(ctx.handle, C.c_void_p(d_col), typ, None, n, base, bits, ptrs))
+    bv = n / 8
+    print(f"--- {name}: {bits} slices, column {elem * n / 1e9:.2f} GB, slices {bits * bv / 1e9:.2f} GB", flush=True)
+
+    def compare():
+        L.check(lib.cubit_bitslice_compare(ctx.handle, ptrs, bits, None, n, 0, (top - base) // 2, 0, words.ptr))
+
+    cmp_ms = [timed(compare) for _ in range(ROUNDS)]
+    cmp_kernel = kernel_ms(compare)
+    line(f"bitslice_compare, one pass over {bits} slices", cmp_ms, (bits + 1) * bv)
+    print(f"bitslice_compare kernel time {cmp_kernel:.3f} ms = {(bits + 1) * bv / cmp_kernel / 1e9:.2f} TB/s", flush=True)
+    for sel_name, c in SELS:
+        fs = F.TableFilterSet({0: F.ConstantFilter("<", c)}) if c is not None else None
+        plan = F.serialize(fs, None)
+        nodes = F.to_ctypes(plan.nodes)
+        est = t.estimate_rows(fs)
+        for ops_name, ops in OPS:
+
+            def call(flag, out):
+                L.check(lib.cubit_table_aggregate(t.handle, nodes, len(plan.nodes), None, col, ops | flag, out.ptr))
+
+            def from_slices():
+                call(L.AGG_FROM_SLICES, out_s)
+
+            def from_column():
+                call(L.AGG_FROM_COLUMN, out_c)
+
+            from_slices()
+            from_column()
+            ctx.sync()
+            a, b = out_s.download(np.int64, 6), out_c.download(np.int64, 6)
+            if not np.array_equal(a, b):
+                print(f"paths differ at {sel_name} {ops_name}: slices {a} column {b}", flush=True)
+                sys.exit(1)
+            call(0, out_s)
+            ctx.sync()
+            chosen = "slices" if t.last_aggregate_from_slices() else "column"
+            res = {"slices": [], "column": []}
+            for r in range(ROUNDS):
+                order = [("slices", from_slices), ("column", from_column)]
+                for what, fn in order[r % 2:] + order[:r % 2]:
+                    res[what].append(timed(fn))
+            k_ms = kernel_ms(from_slices)
+            rows = int(a[5])
+            print(f"{name}; selectivity {sel_name} ({rows} rows, estimate {est}); {ops_name}; path=None takes the {chosen}",
+                  flush=True)
+            line("  from the slices", res["slices"], (bits + 1) * bv)
+            line("  from the column", res["column"])
+            spread = max(max(ms) - min(ms) for ms in res.values())
+            print(f"  slices / column = {min(res['slices']) / min(res['column']):.2f} (largest spread {spread:.3f} ms); "
+                  f"fused kernel {k_ms:.3f} ms = {(bits + 1) * bv / k_ms / 1e9:.2f} TB/s; "
+                  f"fused kernel / compare kernel = {k_ms / cmp_kernel:.2f}", flush=True)
+    slices.free()
+words.free()
+t.close()
+ctx.close()
