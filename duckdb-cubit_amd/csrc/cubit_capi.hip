@@ -1,8 +1,9 @@
 // C ABI of libcubitgpu.so (include/cubit_gpu.h) and the host-side planner that turns a
 // DuckDB-style predicate tree (TableFilter mirror) into bitvector programs for the
 // fused eval/decode kernel. The expressions, the emitter that writes a program and the walk of a
-// filter tree are in cubit_program.hpp (HIP-free, run on the CPU by tests/program_core.cpp); what
-// touches a table or the device is here.
+// filter tree are in cubit_program.hpp (HIP-free, run on the CPU by tests/program_core.cpp), the
+// policy of the kept leaf combinations in cubit_derived.hpp (tests/derived_core.cpp); what touches
+// a table or the device is here.
 //
 // Planner semantics (all exact; a leaf the index cannot answer exactly is built from the raw
 // column — by the candidate check of its bin, or by K0 — never approximated):
@@ -34,6 +35,7 @@
 #include <vector>
 
 #include "../../include/cubit_gpu.h"
+#include "cubit_derived.hpp"
 #include "cubit_internal.hpp"
 
 using namespace cubit;
@@ -987,6 +989,13 @@ struct Updates {
     uint32_t dirty_nz = 0;
 };
 
+// A kept combination of one column's bitvectors (cubit_derived.hpp): the table-owned bitvector
+// that holds it and the leaf later plans put in the group's place.
+struct DerivedLeaf {
+    std::unique_ptr<DevBuf> bv;
+    Leaf leaf;
+};
+
 }  // namespace
 
 struct cubit_table {
@@ -1079,6 +1088,13 @@ struct cubit_table {
     std::vector<int32_t> last_narrow_cols;  // columns of the last plan's K0 leaves, in build order
     bool last_sum_packed = false;  // the last sum_product read a from its BITPACKING segments
     bool last_agg_slices = false;  // the last cubit_table_aggregate read the column's slices
+    // Derived leaves: combinations of one column's table-owned bitvectors that scans keep asking
+    // for (a RANGE interval's L(hi) AND NOT L(lo), a union of EQUALITY / BINS leaves), each kept
+    // as one bitvector once it has been planned often enough (derive_leaves). Dropped with the
+    // zone maps (drop_zones): an entry always holds the combination of the current bits.
+    DerivedCache<DerivedLeaf> derived;
+    std::unordered_set<const uint64_t*> derived_bvs;  // the entries' bitvectors
+    bool derived_budget_set = false;  // cubit_table_set_derived_budget (else: the default share)
 };
 
 namespace {
@@ -1089,6 +1105,17 @@ void drop_zones(cubit_table* t) {
     t->zones.clear();
     t->col_zones.clear();
     t->pred_zones.clear();
+    // the derived leaves combine bits that are about to change: they and their use counters go
+    t->derived.clear([](DerivedLeaf&) {});
+    t->derived_bvs.clear();
+}
+
+// A derived leaf leaves the cache: its zone map goes with it (the map is keyed by pointer, and
+// the address may be handed out again).
+void forget_derived(cubit_table* t, DerivedLeaf& d) {
+    const uint64_t* bv = static_cast<const uint64_t*>(d.bv->p);
+    t->zones.erase(bv);
+    t->derived_bvs.erase(bv);
 }
 
 // The column's values or indexes changed: its patched leaves are stale.
@@ -4074,6 +4101,10 @@ double conj_selectivity(cubit_table* t, const Emitter::Lits& lits, int* rc) {
     for (const auto& lit : lits) {
         const Leaf& l = lit.first;
         const bool neg = lit.second;
+        if (l.sel >= 0.0) {  // a derived leaf that is no interval: the estimate of what it replaced
+            sel *= neg ? 1.0 - l.sel : l.sel;
+            continue;
+        }
         if (l.column < 0 || l.pred == 1) continue;
         auto& r = iv.emplace(l.column, std::make_pair(-inf, inf)).first->second;
         const double c = (double)l.constant;
@@ -4370,6 +4401,139 @@ extern "C" int cubit_table_estimate_rows(cubit_table* t, const cubit_filter_node
 
 namespace {
 
+// ---- derived leaves (policy: cubit_derived.hpp). A pass over the planned expression, before the
+// MVCC patches, the zonemap skip and the split into passes: in every AND chain and every OR chain
+// the literals on table-owned bitvectors of one column form a group (the interval of a RANGE index,
+// L(hi) AND NOT L(lo), with or without the validity leaf; the union of EQUALITY or BINS leaves).
+// A group planned often enough is evaluated once by the bits-only pass into a table-owned
+// bitvector, and this and later plans read that one leaf in its place.
+
+// bytes the derived leaves of a table may hold unless cubit_table_set_derived_budget said
+// otherwise: a quarter of its own index bitvectors
+uint64_t default_derived_budget(const cubit_table* t) {
+    uint64_t n = 0;
+    for (const auto* m : {&t->idx, &t->bins, &t->sliced})
+        for (const auto& kv : *m) n += kv.second.bvs.size();
+    return n * std::max<uint64_t>(t->cap_words, 1) * 8 / 4;
+}
+
+// a literal that may join a group: a table-owned index or validity bitvector as it stands (not a
+// derived leaf: its address can be handed out again), on a column whose leaves this transaction
+// does not see patched
+bool derivable(const cubit_table* t, const ExprP& p, const cubit_txn* txn) {
+    if (p->kind != Expr::LEAF) return false;
+    const Leaf& l = p->leaf;
+    if (l.zsrc != kZoneBits || l.zbv || l.zdirty >= 0 || l.column < 0 || t->derived_bvs.count(l.bv)) return false;
+    auto u = t->upd.find(l.column);
+    return u == t->upd.end() || !u->second.any_visible(txn);
+}
+
+// The group g (literals of column col combined by op) as one leaf when it is kept or admitted
+// now, else *out = null and the plan keeps its literals.
+int derive_group(cubit_table* t, int op, int col, const std::vector<ExprP>& g, ExprP* out) {
+    *out = nullptr;
+    std::vector<DerivedLit> lits;
+    for (const ExprP& p : g) lits.push_back({reinterpret_cast<uintptr_t>(p->leaf.bv), p->neg});
+    DerivedKey key;
+    if (!derived_key(col, op, std::move(lits), &key)) return CUBIT_OK;
+    if (DerivedLeaf* d = t->derived.find(key)) {
+        *out = mk_leaf(d->leaf);
+        return CUBIT_OK;
+    }
+    ExprP e = g[0];
+    for (size_t i = 1; i < g.size(); ++i) e = mk_bin(op == kDerivedAnd ? Expr::AND : Expr::OR, e, g[i]);
+    if (!fits(e)) return CUBIT_OK;
+    const uint64_t bytes = std::max<uint64_t>(t->cap_words, 1) * 8;
+    if (!t->derived.request(key, bytes)) return CUBIT_OK;
+    Leaf l;
+    l.column = col;
+    l.zsrc = kZoneBits;
+    l.pred = 3;
+    if (op == kDerivedAnd) {
+        // L(hi) AND NOT L(lo) of a range index (its rows are valid ones: the validity leaf adds
+        // nothing): the interval lo <= v < hi
+        const Leaf *lo = nullptr, *hi = nullptr;
+        bool interval = true;
+        for (const ExprP& p : g) {
+            const Leaf& x = p->leaf;
+            if (x.pred == 1 && !p->neg) continue;
+            const Leaf*& slot = p->neg ? lo : hi;
+            if (x.pred != 0 || x.cmp != CUBIT_CMP_LT || (slot && slot->bv != x.bv)) interval = false;
+            slot = &x;
+        }
+        if (interval && lo && hi && lo->constant < hi->constant) {
+            l.pred = 2;
+            l.constant = lo->constant;
+            l.constant2 = hi->constant;
+        }
+    }
+    if (l.pred == 3) {
+        int rc = CUBIT_OK;
+        Emitter::Lits c;
+        l.sel = op == kDerivedAnd && Emitter::conj_leaves(e, c) ? conj_selectivity(t, c, &rc) : expr_selectivity(t, e, &rc);
+        if (rc) return rc;
+    }
+    auto b = std::make_unique<DevBuf>();
+    if (alloc_table_bv(t, *b) != CUBIT_OK) {  // no memory to keep it: the plan reads its literals
+        (void)hipGetLastError();
+        return CUBIT_OK;
+    }
+    Emitter em;
+    em.emit_top(e);
+    uint64_t* words = static_cast<uint64_t*>(b->p);
+    t->last_passes++;
+    if (int rc = run_eval(t->ctx, em.prog, t->n_rows, 0, nullptr, 0, t->dummy_count, words, RunMode::kCount)) return rc;
+    l.bv = words;
+    DerivedLeaf d;
+    d.bv = std::move(b);
+    d.leaf = l;
+    t->derived.insert(key, bytes, std::move(d));
+    t->derived_bvs.insert(words);
+    *out = mk_leaf(l);
+    return CUBIT_OK;
+}
+
+int derive_leaves(cubit_table* t, ExprP& e, const cubit_txn* txn) {
+    if (e->kind == Expr::LEAF || e->kind == Expr::CONST_TRUE || e->kind == Expr::CONST_FALSE) return CUBIT_OK;
+    const bool conj = e->kind == Expr::AND || (e->kind == Expr::ANDNOT && e->b->kind == Expr::LEAF);
+    if (!conj && e->kind != Expr::OR) {  // a AND NOT (subtree): each side on its own
+        if (int rc = derive_leaves(t, e->a, txn)) return rc;
+        return derive_leaves(t, e->b, txn);
+    }
+    std::vector<ExprP> parts;
+    if (conj) conj_parts(e, parts);
+    else Emitter::or_parts(e, parts);
+    bool changed = false;
+    std::map<int, std::vector<size_t>> by_col;
+    for (size_t i = 0; i < parts.size(); ++i) {
+        if (parts[i]->kind == Expr::LEAF) {
+            if (derivable(t, parts[i], txn)) by_col[parts[i]->leaf.column].push_back(i);
+            continue;
+        }
+        ExprP q = parts[i];
+        if (int rc = derive_leaves(t, q, txn)) return rc;
+        changed |= q != parts[i];
+        parts[i] = q;
+    }
+    for (const auto& [col, at] : by_col) {
+        if (at.size() < 2) continue;
+        std::vector<ExprP> g;
+        for (size_t i : at) g.push_back(parts[i]);
+        ExprP d;
+        if (int rc = derive_group(t, conj ? kDerivedAnd : kDerivedOr, col, g, &d)) return rc;
+        if (!d) continue;
+        for (size_t i : at) parts[i] = nullptr;
+        parts[at[0]] = d;
+        changed = true;
+    }
+    if (!changed) return CUBIT_OK;  // the expression as the planner built it
+    ExprP acc = conj ? mk_true() : mk_false();
+    for (const ExprP& p : parts)
+        if (p) acc = mk_bin(conj ? Expr::AND : Expr::OR, acc, p);
+    e = acc;
+    return CUBIT_OK;
+}
+
 // Plan a pushed filter tree for a transaction into one program (front half of every scan):
 // planner → MVCC update patches → visibility leaf → constant folding → split until it fits
 // one pass → emit. *empty = the filter is FALSE (no kernel needed). live (optional) receives the
@@ -4401,6 +4565,16 @@ int plan_program(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_node
         if (!e) return p.rc ? p.rc : fail(CUBIT_ERR_INVALID, "planning failed");
         pending = std::move(p.pending);
     }
+    // kept leaf combinations take their groups' places; evictions owed happen first and none
+    // until the plan is complete (its program holds the pointers)
+    auto forget = [t](DerivedLeaf& d) { forget_derived(t, d); };
+    if (!t->derived_budget_set) t->derived.set_budget(default_derived_budget(t), forget);
+    t->derived.begin_plan(forget);
+    struct EndPlan {
+        cubit_table* t;
+        ~EndPlan() { t->derived.end_plan(); }
+    } end_plan{t};
+    if (int rc = derive_leaves(t, e, txn)) return rc;
     // a transaction that sees updates patches whole leaves: build the K0 leaves in full first
     bool visible_updates = false;
     if (txn)
@@ -4890,6 +5064,24 @@ extern "C" int cubit_table_last_plan(cubit_table* t, uint32_t* n_leaves, uint32_
     CUBIT_LOCK(t->ctx);
     if (n_leaves) *n_leaves = t->last_leaves;
     if (n_passes) *n_passes = t->last_passes;
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_set_derived_budget(cubit_table* t, uint64_t bytes) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    if (int rc = set_device(t->ctx)) return rc;
+    t->derived_budget_set = true;
+    t->derived.set_budget(bytes, [t](DerivedLeaf& d) { forget_derived(t, d); });
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_derived_stats(cubit_table* t, uint32_t* leaves, uint64_t* bytes, uint64_t* hits) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    if (leaves) *leaves = (uint32_t)t->derived.size();
+    if (bytes) *bytes = t->derived.bytes();
+    if (hits) *hits = t->derived.hits();
     return CUBIT_OK;
 }
 

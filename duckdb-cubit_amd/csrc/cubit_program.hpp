@@ -245,7 +245,9 @@ inline NodeCheck check_filter_node(const cubit_filter_node& f) {
 struct Leaf {
     const uint64_t* bv = nullptr;
     int column = -1;  // -1: not derived from a column value (visibility, temp)
-    int pred = 0;     // 0 = cmp (v CMP c), 1 = valid (NN), 2 = bin (c <= v < constant2)
+    // 0 = cmp (v CMP c), 1 = valid (NN), 2 = bin (c <= v < constant2), 3 = a kept combination of
+    // the column's bitvectors that is no single interval (a derived leaf; never patched)
+    int pred = 0;
     int cmp = 0;
     int64_t constant = 0;
     int64_t constant2 = 0;
@@ -260,6 +262,8 @@ struct Leaf {
     // column zdirty (there: mixed)
     const uint64_t* zbv = nullptr;
     int zdirty = -1;
+    // pred 3: the estimated fraction of rows it keeps, from the literals it replaced (< 0: none)
+    double sel = -1.0;
 };
 enum { kZoneNone = 0, kZoneBits = 1, kZoneStats = 2 };
 

@@ -734,6 +734,18 @@ class CubitTable:
         L.check(self.lib.cubit_table_last_plan(self.handle, C.byref(k), C.byref(p)))
         return int(k.value), int(p.value)
 
+    def set_derived_budget(self, n_bytes: int) -> None:
+        """Bytes the kept leaf combinations (derived leaves) may hold; 0 turns them off."""
+        L.check(self.lib.cubit_table_set_derived_budget(self.handle, int(n_bytes)))
+
+    def derived_stats(self):
+        """(kept combinations, their bytes, groups replaced by one so far)."""
+        n = C.c_uint32()
+        b = C.c_uint64()
+        h = C.c_uint64()
+        L.check(self.lib.cubit_table_derived_stats(self.handle, C.byref(n), C.byref(b), C.byref(h)))
+        return int(n.value), int(b.value), int(h.value)
+
     def close(self) -> None:
         # a partition never outlives its context (Context.close destroys it first)
         if self.handle and self.ctx.handle:

@@ -687,6 +687,20 @@ int cubit_table_probe_validity(cubit_table *t, int col, const cubit_txn *txn, co
 int cubit_table_estimate_rows(cubit_table *t, const cubit_filter_node *nodes, uint32_t n_nodes, uint64_t *rows);
 /* Bitvectors the last cubit_table_scan read per 64-row word (K) — for roofline bytes. */
 int cubit_table_last_plan(cubit_table *t, uint32_t *n_leaves, uint32_t *n_passes);
+/* Derived leaves. A combination of one column's index / validity bitvectors that scans keep asking
+ * for — a RANGE interval's L(hi) AND NOT L(lo), the union behind an IN-list on an EQUALITY index or
+ * a range over BINS — is evaluated once and kept as one table-owned bitvector, which later plans
+ * read in the combination's place (K falls by k - 1 for a group of k). A combination is kept on
+ * the first request before which uses * (k - 1) >= k + 1 (an interval: the fourth request); that
+ * scan runs one extra bits-only pass, counted in cubit_table_last_plan's n_passes. Results never
+ * change: entries are dropped whenever a table-owned bitvector is written, grown or freed, and a
+ * column whose MVCC updates the reader sees is read through its own (patched) leaves.
+ * `bytes` bounds what the kept bitvectors may hold (default: a quarter of the table's index
+ * bitvectors), the least recently used going first; 0 turns the feature off and frees them. */
+int cubit_table_set_derived_budget(cubit_table *t, uint64_t bytes);
+/* Kept combinations, the bytes they hold, and the groups that plans replaced by one so far
+ * (any pointer may be NULL). */
+int cubit_table_derived_stats(cubit_table *t, uint32_t *leaves, uint64_t *bytes, uint64_t *hits);
 /* Column statistics — DataTable::GetStatistics behind seq_scan's `statistics` callback
  * (TableScanStatistics, src/function/table/table_scan.cpp:108-117): min / max of the valid
  * values (widened by the column's update records, as UpdateSegment merges updates into the

@@ -16,6 +16,9 @@ ROUND = sys.argv[1] if len(sys.argv) > 1 else "r01"
 # the profile tree of one run: gpurun_out/prof (old per-round scripts) or gpurun_out/<out>/prof
 # (scripts/gpu.sh profile:<workload> steps)
 PROF = Path(sys.argv[2]) if len(sys.argv) > 2 else ROOT / "gpurun_out" / "prof"
+# appended to the workload's key in pmc_summary.json: a second profile of one workload (another
+# build of the same tree, say its parent) beside the one bench.py looks up
+SUFFIX = sys.argv[3] if len(sys.argv) > 3 else ""
 KERNELS = ("eval_decode_pairs", "eval_decode_runs", "eval_decode_lookback")  # the bench line names the one it launched
 
 
@@ -140,7 +143,7 @@ def main():
         w_kb = statistics.median(float(r["Counter_Value"]) for r in write)
         dur = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in kt]
         rd, wrb = 2 * f_kb * 1024, w_kb * 1024
-        summary[workload] = {
+        summary[workload + SUFFIX] = {
             "kernel": fetch[0]["Kernel_Name"],
             "launches": len(fetch),
             "FETCH_SIZE_kB_median": f_kb,
@@ -157,7 +160,7 @@ def main():
             "source": f"profiles/{ROUND}_{w}_pmc_*.csv, profiles/{ROUND}_{w}_kernel_stats.csv "
                       "(rocprofv3 --kernel-trace --stats; --pmc FETCH_SIZE; --pmc WRITE_SIZE; separate passes)",
         }
-        print(workload, json.dumps(summary[workload], indent=1))
+        print(workload + SUFFIX, json.dumps(summary[workload + SUFFIX], indent=1))
         k5 = line.get("k5_bitunpack")
         if k5:
             # K5 leg (bench.py --bitpacked): every bitunpack launch of the run, all columns
