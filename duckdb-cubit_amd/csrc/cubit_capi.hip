@@ -994,6 +994,11 @@ struct Updates {
 struct DerivedLeaf {
     std::unique_ptr<DevBuf> bv;
     Leaf leaf;
+    // a chain: what it replaced, and the selectivity estimate made from it the first time a plan
+    // asks (conj_selectivity; < 0 = not yet). The estimate reads the columns' zone statistics,
+    // which a plan that only reads the kept leaf never needs.
+    ExprP replaced;
+    double sel = -1.0;
 };
 
 }  // namespace
@@ -1093,7 +1098,7 @@ struct cubit_table {
     // as one bitvector once it has been planned often enough (derive_leaves). Dropped with the
     // zone maps (drop_zones): an entry always holds the combination of the current bits.
     DerivedCache<DerivedLeaf> derived;
-    std::unordered_set<const uint64_t*> derived_bvs;  // the entries' bitvectors
+    std::unordered_map<const uint64_t*, DerivedLeaf*> derived_bvs;  // the entries by their bitvectors
     bool derived_budget_set = false;  // cubit_table_set_derived_budget (else: the default share)
 };
 
@@ -1126,10 +1131,15 @@ void drop_patches(cubit_table* t, int col) {
 }
 
 // a table-owned bitvector of cap_words words, all zero (the kernels that fill it write nwp
-// words; the rest must stay zero for appends that grow into it)
-int alloc_table_bv(cubit_table* t, DevBuf& b) {
-    if (hipMalloc(&b.p, std::max<uint64_t>(t->cap_words, 1) * 8) != hipSuccess) return CUBIT_ERR_OOM;
-    if (hipMemsetAsync(b.p, 0, std::max<uint64_t>(t->cap_words, 1) * 8, t->ctx->stream) != hipSuccess) return CUBIT_ERR_HIP;
+// words; the rest must stay zero for appends that grow into it). A caller whose next kernel on
+// the stream writes the first `written` words says so, and only the rest is cleared.
+int alloc_table_bv(cubit_table* t, DevBuf& b, uint64_t written = 0) {
+    const uint64_t words = std::max<uint64_t>(t->cap_words, 1);
+    if (hipMalloc(&b.p, words * 8) != hipSuccess) return CUBIT_ERR_OOM;
+    written = std::min(written, words);
+    if (written < words &&
+        hipMemsetAsync(static_cast<uint64_t*>(b.p) + written, 0, (words - written) * 8, t->ctx->stream) != hipSuccess)
+        return CUBIT_ERR_HIP;
     return CUBIT_OK;
 }
 
@@ -4105,6 +4115,26 @@ double conj_selectivity(cubit_table* t, const Emitter::Lits& lits, int* rc) {
             sel *= neg ? 1.0 - l.sel : l.sel;
             continue;
         }
+        if (l.pred == 3 && l.column < 0) {  // a kept chain: the estimate of what it replaced, made once
+            auto it = t->derived_bvs.find(l.bv);
+            if (it == t->derived_bvs.end()) continue;
+            DerivedLeaf& d = *it->second;
+            if (d.sel < 0.0) {
+                std::vector<ExprP> parts;
+                conj_parts(d.replaced, parts);
+                Emitter::Lits c;
+                double s = 1.0;
+                for (const ExprP& p : parts) {
+                    if (p->kind == Expr::LEAF) c.push_back({p->leaf, p->neg});
+                    else s *= expr_selectivity(t, p, rc);
+                }
+                s *= conj_selectivity(t, c, rc);
+                if (*rc) return 1.0;
+                d.sel = std::min(1.0, std::max(0.0, s));
+            }
+            sel *= neg ? 1.0 - d.sel : d.sel;
+            continue;
+        }
         if (l.column < 0 || l.pred == 1) continue;
         auto& r = iv.emplace(l.column, std::make_pair(-inf, inf)).first->second;
         const double c = (double)l.constant;
@@ -4406,7 +4436,14 @@ namespace {
 // the literals on table-owned bitvectors of one column form a group (the interval of a RANGE index,
 // L(hi) AND NOT L(lo), with or without the validity leaf; the union of EQUALITY or BINS leaves).
 // A group planned often enough is evaluated once by the bits-only pass into a table-owned
-// bitvector, and this and later plans read that one leaf in its place.
+// bitvector, and this and later plans read that one leaf in its place. In every AND chain (those
+// under an OR included) the derivable literals of all columns together, with the unions of one
+// column's leaves, form a chain: a repeated WHERE clause. A kept chain is looked up first and one
+// leaf replaces all its literals; otherwise the column groups take theirs, the chain's request is
+// counted, and it is bought by cost (derived_chain_admit) from what the plan reads in its place.
+// Literals that are not derivable (K0, candidate-check, sliced and scratch leaves, a column whose
+// update records the transaction sees; the visibility leaf is added later) stay outside and are
+// ANDed with the kept leaf.
 
 // bytes the derived leaves of a table may hold unless cubit_table_set_derived_budget said
 // otherwise: a quarter of its own index bitvectors
@@ -4426,6 +4463,31 @@ bool derivable(const cubit_table* t, const ExprP& p, const cubit_txn* txn) {
     if (l.zsrc != kZoneBits || l.zbv || l.zdirty >= 0 || l.column < 0 || t->derived_bvs.count(l.bv)) return false;
     auto u = t->upd.find(l.column);
     return u == t->upd.end() || !u->second.any_visible(txn);
+}
+
+// Evaluate e (the combination `key` names, as the plan reads it now) with the bits-only pass into
+// a table-owned bitvector, keep it under `key` and hand out the leaf l on it. *out stays null
+// when there is no memory to keep it: the plan reads its literals.
+int keep_derived(cubit_table* t, const DerivedKey& key, uint64_t bytes, const ExprP& e, Leaf l, ExprP* out) {
+    const bool is_chain = derived_is_chain(key);
+    auto b = std::make_unique<DevBuf>();
+    if (alloc_table_bv(t, *b, padded_words(t->n_rows)) != CUBIT_OK) {  // the pass below writes those words
+        (void)hipGetLastError();
+        return CUBIT_OK;
+    }
+    Emitter em;
+    em.emit_top(e);
+    uint64_t* words = static_cast<uint64_t*>(b->p);
+    t->last_passes++;
+    if (int rc = run_eval(t->ctx, em.prog, t->n_rows, 0, nullptr, 0, t->dummy_count, words, RunMode::kCount)) return rc;
+    l.bv = words;
+    DerivedLeaf d;
+    d.bv = std::move(b);
+    d.leaf = l;
+    if (is_chain) d.replaced = e;
+    t->derived_bvs[words] = t->derived.insert(key, bytes, std::move(d));
+    *out = mk_leaf(l);
+    return CUBIT_OK;
 }
 
 // The group g (literals of column col combined by op) as one leaf when it is kept or admitted
@@ -4473,24 +4535,42 @@ int derive_group(cubit_table* t, int op, int col, const std::vector<ExprP>& g, E
         l.sel = op == kDerivedAnd && Emitter::conj_leaves(e, c) ? conj_selectivity(t, c, &rc) : expr_selectivity(t, e, &rc);
         if (rc) return rc;
     }
-    auto b = std::make_unique<DevBuf>();
-    if (alloc_table_bv(t, *b) != CUBIT_OK) {  // no memory to keep it: the plan reads its literals
-        (void)hipGetLastError();
-        return CUBIT_OK;
+    return keep_derived(t, key, bytes, e, l, out);
+}
+
+// The chain `key` (the AND of g: what the plan reads in its place now, kept column groups and
+// unions included) as one leaf when it is admitted now, else *out = null. The leaf has no column:
+// it takes its zone classes from its own bits, and the conjunction's selectivity estimate from
+// its entry (made from what it replaced when a plan first asks: conj_selectivity).
+int derive_chain(cubit_table* t, const DerivedKey& key, const std::vector<ExprP>& g, ExprP* out) {
+    *out = nullptr;
+    ExprP e = g[0];
+    for (size_t i = 1; i < g.size(); ++i) e = mk_bin(Expr::AND, e, g[i]);
+    if (!fits(e)) return CUBIT_OK;
+    std::vector<const uint64_t*> bvs;
+    leaves_of(e, bvs);
+    std::sort(bvs.begin(), bvs.end());
+    const uint64_t k = std::unique(bvs.begin(), bvs.end()) - bvs.begin();
+    const uint64_t bytes = std::max<uint64_t>(t->cap_words, 1) * 8;
+    if (!t->derived.request(key, bytes, k)) return CUBIT_OK;
+    Leaf l;
+    l.zsrc = kZoneBits;
+    l.pred = 3;
+    return keep_derived(t, key, bytes, e, l, out);
+}
+
+// the key of an OR group that is the union of one column's derivable leaves and nothing else (an
+// IN-list on an EQUALITY index, a range over BINS): it may join a chain
+bool union_key(const cubit_table* t, const ExprP& p, const cubit_txn* txn, DerivedKey* key) {
+    if (p->kind != Expr::OR) return false;
+    std::vector<ExprP> parts;
+    Emitter::or_parts(p, parts);
+    std::vector<DerivedLit> lits;
+    for (const ExprP& q : parts) {
+        if (!derivable(t, q, txn) || q->leaf.column != parts[0]->leaf.column) return false;
+        lits.push_back({reinterpret_cast<uintptr_t>(q->leaf.bv), q->neg});
     }
-    Emitter em;
-    em.emit_top(e);
-    uint64_t* words = static_cast<uint64_t*>(b->p);
-    t->last_passes++;
-    if (int rc = run_eval(t->ctx, em.prog, t->n_rows, 0, nullptr, 0, t->dummy_count, words, RunMode::kCount)) return rc;
-    l.bv = words;
-    DerivedLeaf d;
-    d.bv = std::move(b);
-    d.leaf = l;
-    t->derived.insert(key, bytes, std::move(d));
-    t->derived_bvs.insert(words);
-    *out = mk_leaf(l);
-    return CUBIT_OK;
+    return derived_key(parts[0]->leaf.column, kDerivedOr, std::move(lits), key);
 }
 
 int derive_leaves(cubit_table* t, ExprP& e, const cubit_txn* txn) {
@@ -4505,11 +4585,41 @@ int derive_leaves(cubit_table* t, ExprP& e, const cubit_txn* txn) {
     else Emitter::or_parts(e, parts);
     bool changed = false;
     std::map<int, std::vector<size_t>> by_col;
+    // the chain of an AND chain: its derivable literals and its unions of one column's leaves
+    std::vector<size_t> chain_at;
+    std::vector<ChainLit> chain_lits;
+    std::vector<DerivedKey> chain_unions;
     for (size_t i = 0; i < parts.size(); ++i) {
         if (parts[i]->kind == Expr::LEAF) {
-            if (derivable(t, parts[i], txn)) by_col[parts[i]->leaf.column].push_back(i);
+            if (!derivable(t, parts[i], txn)) continue;
+            const Leaf& l = parts[i]->leaf;
+            by_col[l.column].push_back(i);
+            if (conj) {
+                chain_at.push_back(i);
+                chain_lits.push_back({l.column, {reinterpret_cast<uintptr_t>(l.bv), parts[i]->neg}});
+            }
             continue;
         }
+        DerivedKey u;
+        if (conj && union_key(t, parts[i], txn, &u)) {
+            chain_at.push_back(i);
+            chain_unions.push_back(std::move(u));
+        }
+    }
+    // the whole chain kept: one leaf in the place of all its literals
+    DerivedKey chain;
+    bool chain_wanted = conj && derived_chain_key(chain_lits, std::move(chain_unions), &chain);
+    if (chain_wanted) {
+        if (DerivedLeaf* d = t->derived.find(chain)) {
+            for (size_t i : chain_at) parts[i] = nullptr;
+            parts[chain_at[0]] = mk_leaf(d->leaf);
+            by_col.clear();
+            chain_wanted = false;
+            changed = true;
+        }
+    }
+    for (size_t i = 0; i < parts.size(); ++i) {
+        if (!parts[i] || parts[i]->kind == Expr::LEAF) continue;
         ExprP q = parts[i];
         if (int rc = derive_leaves(t, q, txn)) return rc;
         changed |= q != parts[i];
@@ -4525,6 +4635,20 @@ int derive_leaves(cubit_table* t, ExprP& e, const cubit_txn* txn) {
         for (size_t i : at) parts[i] = nullptr;
         parts[at[0]] = d;
         changed = true;
+    }
+    // no entry: the chain's request counts, with what the plan reads in its place after the column
+    // groups took theirs
+    if (chain_wanted) {
+        std::vector<ExprP> g;
+        for (size_t i : chain_at)
+            if (parts[i]) g.push_back(parts[i]);
+        ExprP d;
+        if (int rc = derive_chain(t, chain, g, &d)) return rc;
+        if (d) {
+            for (size_t i : chain_at) parts[i] = nullptr;
+            parts[chain_at[0]] = d;
+            changed = true;
+        }
     }
     if (!changed) return CUBIT_OK;  // the expression as the planner built it
     ExprP acc = conj ? mk_true() : mk_false();
@@ -5073,6 +5197,21 @@ extern "C" int cubit_table_set_derived_budget(cubit_table* t, uint64_t bytes) {
     if (int rc = set_device(t->ctx)) return rc;
     t->derived_budget_set = true;
     t->derived.set_budget(bytes, [t](DerivedLeaf& d) { forget_derived(t, d); });
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_set_derived_chain_cost(cubit_table* t, uint64_t fixed_bytes) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    t->derived.set_chain_cost(fixed_bytes);
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_derived_chain_stats(cubit_table* t, uint32_t* chains, uint64_t* hits) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    if (chains) *chains = (uint32_t)t->derived.chain_size();
+    if (hits) *hits = t->derived.chain_hits();
     return CUBIT_OK;
 }
 

@@ -8,9 +8,15 @@
 // scans read that one bitvector. The bitvectors held are bounded by a byte budget, the least
 // recently used going first, and nothing is evicted while a plan is being built (a plan holds the
 // pointers it has looked up until its kernel is launched).
+//
+// A second kind of key, the chain, names the derivable literals of one AND chain that lie on two or
+// more columns (a repeated WHERE clause: the same conjunction over several indexed columns). It is
+// kept by the same cache under the same budget, and bought by cost, not by count: see
+// derived_chain_admit.
 #pragma once
 
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 #include <list>
 #include <map>
@@ -51,11 +57,76 @@ inline bool derived_key(int column, int op, std::vector<DerivedLit> lits, Derive
     return true;
 }
 
+// The column of every chain key: no table column has it, so no chain key equals a column's key.
+constexpr int kDerivedChainColumn = INT_MIN;
+
+inline bool derived_is_chain(const DerivedKey& k) { return k.column == kDerivedChainColumn; }
+
+// One literal of an AND chain that may join a chain key, with the column it lies on.
+struct ChainLit {
+    int column;
+    DerivedLit lit;
+};
+
+// The canonical key of an AND chain over several columns: its plain literals and its unions (each the
+// key derived_key gave for an OR group of one column, as an IN-list plans). Always on the base
+// bitvectors, never on a kept group's own bitvector, whose address can be handed out again. The
+// order of the literals, of the unions and inside a union does not matter. The key holds the sorted
+// literals, then per union a separator ({0, true}: no bitvector lies at 0) and the union's literals.
+// False when the chain lies on fewer than two columns, or a bitvector appears both plain and
+// complemented among the literals.
+inline bool derived_chain_key(const std::vector<ChainLit>& chain, std::vector<DerivedKey> unions, DerivedKey* out) {
+    std::vector<int> columns;
+    std::vector<DerivedLit> lits;
+    for (const ChainLit& c : chain) {
+        columns.push_back(c.column);
+        lits.push_back(c.lit);
+    }
+    for (const DerivedKey& u : unions) {
+        if (u.op != kDerivedOr || derived_is_chain(u)) return false;
+        columns.push_back(u.column);
+    }
+    std::sort(columns.begin(), columns.end());
+    if (std::unique(columns.begin(), columns.end()) - columns.begin() < 2) return false;
+    std::sort(lits.begin(), lits.end());
+    lits.erase(std::unique(lits.begin(), lits.end()), lits.end());
+    for (size_t i = 1; i < lits.size(); ++i)
+        if (lits[i].first == lits[i - 1].first) return false;
+    std::sort(unions.begin(), unions.end());
+    unions.erase(std::unique(unions.begin(), unions.end()), unions.end());
+    for (const DerivedKey& u : unions) {
+        lits.push_back({0, true});
+        lits.insert(lits.end(), u.lits.begin(), u.lits.end());
+    }
+    out->column = kDerivedChainColumn;
+    out->op = kDerivedAnd;
+    out->lits = std::move(lits);
+    return true;
+}
+
 // Rent or buy: materialising a combination of k bitvectors costs k reads and one write, and each
 // later scan saves k - 1 reads. It is bought on the first request before which renting has
 // already cost as much: uses_so_far * (k - 1) >= k + 1, uses_so_far being the requests before this
 // one (an interval, k = 2: the fourth request; with a validity leaf, k = 3: the third).
 inline bool derived_admit(uint64_t uses_so_far, uint64_t k) { return k >= 2 && uses_so_far * (k - 1) >= k + 1; }
+
+// A chain is bought by cost. Renting has cost uses_so_far * (k - 1) * B bytes so far (k: the leaves the
+// plan reads in the chain's place, B: the bytes of one bitvector); buying costs the (k + 1) * B of the
+// materialising pass and F, the fixed cost of an admitting scan in byte-equivalents (the allocation,
+// the clear, the zone-class pass and its read-back). F = 0 is derived_admit; F = UINT64_MAX never
+// buys. A small table (B far below F) needs thousands of requests: a one-off query pays nothing.
+inline bool derived_chain_admit(uint64_t uses_so_far, uint64_t k, uint64_t B, uint64_t F) {
+    if (k < 2 || F == UINT64_MAX) return false;
+    using u128 = unsigned __int128;
+    return (u128)uses_so_far * (k - 1) * B >= (u128)(k + 1) * B + F;
+}
+
+// F unless cubit_table_set_derived_chain_cost says otherwise, measured on an MI355X at TPC-H SF100
+// (DESIGN.md §3): the scan that admitted the l_discount interval took 413 µs longer than the plain
+// scans after it, 38 µs of them the bits-only pass's own 225 MB; the other 376 µs at the 5.97 TB/s
+// of that scan's byte mix. SF100 Q6 (k = 3, B = 75 MB) is bought at its 18th request; a 300,001-row
+// table (B = 131 KB as allocated) would need some 8,500.
+constexpr uint64_t kDerivedChainCost = 2'240'000'000ull;
 
 // The cache of materialised combinations (payload P: whatever owns the bitvector) and the use
 // counters of those not materialised yet.
@@ -73,7 +144,12 @@ class DerivedCache {
     uint64_t budget() const { return budget_; }
     uint64_t bytes() const { return bytes_; }
     size_t size() const { return lru_.size(); }
-    uint64_t hits() const { return hits_; }
+    uint64_t hits() const { return hits_; }  // of both kinds
+    size_t chain_size() const { return chains_; }
+    uint64_t chain_hits() const { return chain_hits_; }
+    uint64_t chain_cost() const { return chain_cost_; }
+    // F of derived_chain_admit; counters keep counting under the new value
+    void set_chain_cost(uint64_t fixed_bytes) { chain_cost_ = fixed_bytes; }
     size_t counters() const { return uses_.size(); }
     bool in_plan() const { return in_plan_; }
 
@@ -100,14 +176,16 @@ class DerivedCache {
         if (it == index_.end()) return nullptr;
         lru_.splice(lru_.begin(), lru_, it->second);
         ++hits_;
+        if (derived_is_chain(key)) ++chain_hits_;
         return &it->second->payload;
     }
 
     // One more scan planned `key` (k literals, entry_bytes to keep it) and found no entry. True
     // when it is to be materialised now: the admission rule holds and the budget has room. When
     // only room is missing, the least recently used entries go at the next begin_plan and a
-    // later request is admitted.
-    bool request(const DerivedKey& key, uint64_t entry_bytes) {
+    // later request is admitted. A chain key passes k, the leaves the plan reads in its place at
+    // this moment (after the column groups took theirs), and is admitted by cost.
+    bool request(const DerivedKey& key, uint64_t entry_bytes, uint64_t k = 0) {
         if (budget_ == 0 || entry_bytes > budget_) return false;
         auto it = uses_.find(key);
         if (it == uses_.end()) {
@@ -115,7 +193,9 @@ class DerivedCache {
             it = uses_.emplace(key, 0).first;
         }
         const uint64_t uses_so_far = it->second++;
-        if (!derived_admit(uses_so_far, key.lits.size())) return false;
+        if (derived_is_chain(key) ? !derived_chain_admit(uses_so_far, k, entry_bytes, chain_cost_)
+                                  : !derived_admit(uses_so_far, key.lits.size()))
+            return false;
         if (bytes_ + entry_bytes > budget_) {
             want_ = std::max(want_, entry_bytes);
             return false;
@@ -129,6 +209,7 @@ class DerivedCache {
         lru_.push_front(Entry{key, entry_bytes, std::move(payload)});
         index_[key] = lru_.begin();
         bytes_ += entry_bytes;
+        chains_ += derived_is_chain(key);
         return &lru_.front().payload;
     }
 
@@ -152,6 +233,7 @@ class DerivedCache {
         index_.clear();
         uses_.clear();
         bytes_ = 0;
+        chains_ = 0;
         want_ = 0;
     }
 
@@ -166,6 +248,7 @@ class DerivedCache {
             Entry& e = lru_.back();
             on_evict(e.payload);
             bytes_ -= e.bytes;
+            chains_ -= derived_is_chain(e.key);
             index_.erase(e.key);
             lru_.pop_back();
         }
@@ -174,6 +257,9 @@ class DerivedCache {
     uint64_t budget_ = 0;
     uint64_t bytes_ = 0;
     uint64_t hits_ = 0;
+    uint64_t chain_hits_ = 0;
+    size_t chains_ = 0;  // entries with a chain key
+    uint64_t chain_cost_ = kDerivedChainCost;
     uint64_t want_ = 0;  // room a declined admission asked for
     bool in_plan_ = false;
     std::list<Entry> lru_;  // front = most recently used

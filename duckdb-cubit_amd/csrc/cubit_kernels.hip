@@ -1219,7 +1219,10 @@ __device__ __forceinline__ void stage_by_rank(uint64_t w0, uint64_t w1, uint32_t
     __builtin_amdgcn_wave_barrier();
 }
 
-template <int K, int FORM, int STAGE, int WPC, int SAUX = 16, int DBG = 0, int THREADS = 512>
+// PRE: an instantiation for launches with EvalArgs::tile_prefix only. Nothing is published or
+// waited for, so a dense tile's result words stay in registers and neither s_words nor the
+// recount's list take LDS: four workgroups share a CU where three did.
+template <int K, int FORM, int STAGE, int WPC, int SAUX = 16, int DBG = 0, int THREADS = 512, bool PRE = false>
 __global__ __launch_bounds__(THREADS, WPC * THREADS / 256) void eval_decode_lookback(EvalArgs a,
                                                                                     uint64_t* __restrict__ dir) {
     constexpr int PAIRS = 2, NW = 2 * PAIRS, NWAVES = THREADS / 64;
@@ -1229,11 +1232,12 @@ __global__ __launch_bounds__(THREADS, WPC * THREADS / 256) void eval_decode_look
     __shared__ uint64_t s_pre[NWAVES];
     __shared__ uint32_t s_expired;
     __shared__ uint32_t s_list_n;
-    __shared__ uint32_t s_list_scratch[THREADS];
+    __shared__ uint32_t s_list_scratch[PRE ? 1 : THREADS];
     __shared__ uint32_t s_stage[STAGE];
     // a dense tile's result words, kept here across the look-back walk (16 KiB: three workgroups
     // per CU still fit the 160 KiB) instead of being read and evaluated a second time
-    __shared__ uint64_t s_words[(uint32_t)THREADS * 2 * PAIRS];
+    __shared__ uint64_t s_words[PRE ? 1 : (uint32_t)THREADS * 2 * PAIRS];
+    static_assert(!PRE || !(DBG & 128), "the by-rank stage uses s_words");
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const uint32_t b = blockIdx.x;
     const uint32_t tile = tile_at(a, b);
@@ -1243,7 +1247,7 @@ __global__ __launch_bounds__(THREADS, WPC * THREADS / 256) void eval_decode_look
     // with per-tile counts known up front (a single index leaf: EvalArgs::tile_prefix) the
     // offset is one load, issued here so that it lands while the tile is read and decoded, and
     // no workgroup publishes or waits
-    const bool prefixed = a.tile_prefix != nullptr;
+    const bool prefixed = PRE || a.tile_prefix != nullptr;
     const uint64_t known_base = prefixed ? a.tile_prefix[tile] : 0;
     if (t == 0) s_expired = 0;
     u64x2 v[K][PAIRS];
@@ -1283,11 +1287,11 @@ __global__ __launch_bounds__(THREADS, WPC * THREADS / 256) void eval_decode_look
         __hip_atomic_store(a.flags + b, (a.epoch << kFlagCntBits) | (uint64_t)tile_count, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     const bool staged = tile_count <= (uint32_t)STAGE;
-    if (!staged && write_ids && !(DBG & 2)) {
+    if (!PRE && !staged && write_ids && !(DBG & 2)) {
 #pragma unroll
         for (int j = 0; j < NW; ++j) s_words[(uint32_t)j * THREADS + t] = r[j];
     }
-    if ((DBG & 128) && staged && write_ids && tile_count) {
+    if (!PRE && (DBG & 128) && staged && write_ids && tile_count) {
         // every lane takes ids lane, lane + 64, … of its wave's slice of each pair
 #pragma unroll
         for (int p = 0; p < PAIRS; ++p) {
@@ -1350,7 +1354,7 @@ __global__ __launch_bounds__(THREADS, WPC * THREADS / 256) void eval_decode_look
     for (int w = 0; w < NWAVES; ++w) base += s_pre[w];
     if (prefixed) {
         base = known_base;
-    } else if (s_expired) {
+    } else if (!PRE && s_expired) {
         // some earlier tile was not published within the limit: every flag once more, the
         // missing tiles counted here (s_pre and s_wave_tot are free again; s_stage is not)
         base = lookback_recount<K, FORM, THREADS, PAIRS>(a, b, t, s_list_scratch, &s_list_n, s_pre);
@@ -1371,8 +1375,10 @@ __global__ __launch_bounds__(THREADS, WPC * THREADS / 256) void eval_decode_look
     // dense tile: rounds of STAGE ids through the stage, its result words back from s_words (no
     // word is held in registers across the look-back walk and its expiry recount; reading and
     // evaluating the tile a second time instead cost 39.2 vs 30.7 µs for 673 dense tiles)
+    if (!PRE) {
 #pragma unroll
-    for (int j = 0; j < NW; ++j) r[j] = s_words[(uint32_t)j * THREADS + t];
+        for (int j = 0; j < NW; ++j) r[j] = s_words[(uint32_t)j * THREADS + t];
+    }
     for (uint32_t r0 = 0; r0 < tile_count; r0 += (uint32_t)STAGE) {
         const uint32_t r1 = min(tile_count, r0 + (uint32_t)STAGE);
         if (r0) __syncthreads();  // the previous round's copy-out is done
@@ -3962,6 +3968,12 @@ hipError_t dispatch_k_form(const EvalProgram& prog, const F& f) {
 // stage entries (32 KiB of LDS per workgroup)
 constexpr int lookback_wpc(uint32_t) { return 3; }  // 80 VGPRs: no spill for K ≤ 8 (4 per CU: 64, spills)
 constexpr int kLookbackStage = 8192;
+// the same kernel for one leaf whose per-tile offsets are known (EvalArgs::tile_prefix; PRE): 32 KiB
+// of LDS and 50 VGPRs, so four workgroups per CU, all its 32 wave slots. SF100 Q6 kept as one leaf
+// (4,578 tiles of about 2,500 ids): 30.5 µs a step against 35.0 µs with three; a stage of 4,096
+// entries measured the same (30.8), one of 2,048 (most tiles in rounds) 37.8
+// (profiles/r13_prefixed_decode.txt)
+constexpr int kPrefixedWpc = 4;
 uint32_t lookback_max_tiles(uint32_t n_leaves, int n_cus) {
     return std::min<uint32_t>(kLookbackMaxTiles, (uint32_t)lookback_wpc(n_leaves) * (uint32_t)n_cus);
 }
@@ -3983,7 +3995,10 @@ template <int K, int FORM>
 void launch_decode_kf(const EvalArgs& a, uint64_t* dir, unsigned grid, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
                       int kernel, int n_cus) {
     const int which = decode_kernel_for(K, a.num_tiles, grid, kernel, a.live != nullptr, n_cus, a.tile_prefix != nullptr);
-    if (which == 3)
+    if (which == 3 && K == 1 && a.tile_prefix)
+        hipExtLaunchKernelGGL((eval_decode_lookback<1, FORM, kLookbackStage, kPrefixedWpc, 16, 0, 512, true>),
+                              dim3(a.num_tiles), dim3(512), 0, s, e0, e1, 0, a, dir);
+    else if (which == 3)
         hipExtLaunchKernelGGL((eval_decode_lookback<K, FORM, kLookbackStage, lookback_wpc(K)>), dim3(a.num_tiles),
                               dim3(512), 0, s, e0, e1, 0, a, dir);
     else if (which == 2)

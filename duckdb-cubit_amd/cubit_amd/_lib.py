@@ -179,6 +179,8 @@ GPU_SIGNATURES = {
     "cubit_table_last_plan": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U32)]),
     "cubit_table_set_derived_budget": (C.c_int, [_P, _U64]),
     "cubit_table_derived_stats": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U64), C.POINTER(_U64)]),
+    "cubit_table_set_derived_chain_cost": (C.c_int, [_P, _U64]),
+    "cubit_table_derived_chain_stats": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U64)]),
     "cubit_table_estimate_rows": (C.c_int, [_P, C.POINTER(FilterNode), _U32, C.POINTER(_U64)]),
     "cubit_table_last_zones": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U32)]),
     "cubit_table_use_packed_filter": (C.c_int, [_P, C.c_int]),

@@ -746,6 +746,18 @@ class CubitTable:
         L.check(self.lib.cubit_table_derived_stats(self.handle, C.byref(n), C.byref(b), C.byref(h)))
         return int(n.value), int(b.value), int(h.value)
 
+    def set_derived_chain_cost(self, fixed_bytes: int) -> None:
+        """The fixed cost of a scan that admits a chain (a conjunction over several columns kept as one
+        leaf), in bytes; 0 = admit by count like a column group, 2**64 - 1 = never."""
+        L.check(self.lib.cubit_table_set_derived_chain_cost(self.handle, int(fixed_bytes)))
+
+    def derived_chain_stats(self):
+        """(kept chains, chains replaced by one leaf so far); both are part of derived_stats too."""
+        n = C.c_uint32()
+        h = C.c_uint64()
+        L.check(self.lib.cubit_table_derived_chain_stats(self.handle, C.byref(n), C.byref(h)))
+        return int(n.value), int(h.value)
+
     def close(self) -> None:
         # a partition never outlives its context (Context.close destroys it first)
         if self.handle and self.ctx.handle:

@@ -701,6 +701,18 @@ int cubit_table_set_derived_budget(cubit_table *t, uint64_t bytes);
 /* Kept combinations, the bytes they hold, and the groups that plans replaced by one so far
  * (any pointer may be NULL). */
 int cubit_table_derived_stats(cubit_table *t, uint32_t *leaves, uint64_t *bytes, uint64_t *hits);
+/* Chains: the derivable literals of one AND chain that lie on two or more columns (a repeated WHERE
+ * clause, such as TPC-H Q6's three columns) are kept as one bitvector too, under the same budget and
+ * LRU. A chain is bought by cost: on the first request before which
+ * uses * (k - 1) * B >= (k + 1) * B + fixed_bytes, B the bytes of one bitvector, k the bitvectors the
+ * plan reads in the chain's place, fixed_bytes the fixed cost of an admitting scan expressed in bytes
+ * (default: measured, cubit_derived.hpp). A small table needs thousands of requests, so a one-off
+ * query pays nothing. 0 makes it the count rule of the column groups; UINT64_MAX never keeps a
+ * chain (kept ones stay until evicted or invalidated). */
+int cubit_table_set_derived_chain_cost(cubit_table *t, uint64_t fixed_bytes);
+/* Kept chains (counted in cubit_table_derived_stats' leaves and bytes too) and the chains that plans
+ * replaced by one leaf so far (counted in its hits too). Any pointer may be NULL. */
+int cubit_table_derived_chain_stats(cubit_table *t, uint32_t *chains, uint64_t *hits);
 /* Column statistics — DataTable::GetStatistics behind seq_scan's `statistics` callback
  * (TableScanStatistics, src/function/table/table_scan.cpp:108-117): min / max of the valid
  * values (widened by the column's update records, as UpdateSegment merges updates into the
