@@ -83,6 +83,14 @@ struct cubit_ctx {
     uint64_t tmp_cap = 0;
     int64_t* partials = nullptr;
     int64_t* agg = nullptr;      // workspace of the aggregate kernels (kAggWorkspace int64)
+    // the grouped aggregate's workspace (kGroupWorkspace int64) and the slot keys of its column path
+    // (2 × CUBIT_AGG_MAX_GROUPS int64, staged in page-locked memory like the live-tile list),
+    // allocated by the first grouped call (ensure_grouped)
+    int64_t* gagg = nullptr;
+    int64_t* gkeys_dev = nullptr;
+    int64_t* gkeys_host = nullptr;
+    hipEvent_t gkeys_ev = nullptr;
+    bool gkeys_pending = false;
     uint64_t* ticket = nullptr;  // claim ticket of the evaluate kernels (EvalArgs::ticket)
     uint64_t* flags = nullptr;   // look-back flag words of eval_decode_lookback (EvalArgs::flags)
     uint64_t epoch = 0;          // the last look-back launch's epoch (EvalArgs::epoch)
@@ -384,6 +392,11 @@ int cubit_ctx_destroy(cubit_ctx* ctx) {
     if (ctx->tmp_ids) (void)hipFree(ctx->tmp_ids);
     if (ctx->partials) (void)hipFree(ctx->partials);
     if (ctx->agg) (void)hipFree(ctx->agg);
+    if (ctx->gkeys_pending) (void)hipEventSynchronize(ctx->gkeys_ev);
+    if (ctx->gagg) (void)hipFree(ctx->gagg);
+    if (ctx->gkeys_dev) (void)hipFree(ctx->gkeys_dev);
+    if (ctx->gkeys_host) (void)hipHostFree(ctx->gkeys_host);
+    if (ctx->gkeys_ev) (void)hipEventDestroy(ctx->gkeys_ev);
     if (ctx->ticket) (void)hipFree(ctx->ticket);
     if (ctx->flags) (void)hipFree(ctx->flags);
     if (ctx->live_pending) (void)hipEventSynchronize(ctx->live_ev);
@@ -1093,6 +1106,9 @@ struct cubit_table {
     std::vector<int32_t> last_narrow_cols;  // columns of the last plan's K0 leaves, in build order
     bool last_sum_packed = false;  // the last sum_product read a from its BITPACKING segments
     bool last_agg_slices = false;  // the last cubit_table_aggregate read the column's slices
+    // the last cubit_table_aggregate_grouped: its path, group count and fused-kernel launches
+    bool last_grouped_slices = false;
+    uint32_t last_grouped_groups = 0, last_grouped_launches = 0;
     // Derived leaves: combinations of one column's table-owned bitvectors that scans keep asking
     // for (a RANGE interval's L(hi) AND NOT L(lo), a union of EQUALITY / BINS leaves), each kept
     // as one bitvector once it has been planned often enough (derive_leaves). Dropped with the
@@ -5180,6 +5196,285 @@ extern "C" int cubit_table_last_aggregate(cubit_table* t, int* from_slices) {
     if (!t || !from_slices) return fail(CUBIT_ERR_INVALID, "null argument");
     CUBIT_LOCK(t->ctx);
     *from_slices = t->last_agg_slices ? 1 : 0;
+    return CUBIT_OK;
+}
+
+namespace {
+
+// A group column of cubit_table_aggregate_grouped and its slots (group_slots, cubit_program.hpp)
+struct GroupCol {
+    int col = -1;
+    const Column* c = nullptr;
+    const Index* ix = nullptr;
+    const Updates* upd = nullptr;
+    GroupSlots slots;
+};
+// a group leaf: the bitvector, whether it is a validity to complement (the NULL slot), its slot
+struct GroupLeaf {
+    const uint64_t* bv;
+    bool neg;
+    uint32_t slot;
+};
+
+int group_columns(cubit_table* t, const int* group_cols, uint32_t n_group_cols, GroupCol (&gc)[CUBIT_AGG_MAX_GROUP_COLS],
+                  uint32_t* n1, uint32_t* n2) {
+    if (n_group_cols == 0) return fail(CUBIT_ERR_INVALID, "no group column");
+    if (n_group_cols > CUBIT_AGG_MAX_GROUP_COLS)
+        return fail(CUBIT_ERR_UNSUPPORTED, "%u group columns (at most %d)", n_group_cols, CUBIT_AGG_MAX_GROUP_COLS);
+    for (uint32_t k = 0; k < n_group_cols; ++k) {
+        GroupCol& g = gc[k];
+        g.col = group_cols[k];
+        auto cit = t->cols.find(g.col);
+        if (cit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "group column %d not registered", g.col);
+        g.c = &cit->second;
+        auto iit = t->idx.find(g.col);
+        if (iit == t->idx.end() || iit->second.encoding != CUBIT_INDEX_EQUALITY || !iit->second.exact_all)
+            return fail(CUBIT_ERR_UNSUPPORTED, "group column %d has no EQUALITY index over every distinct value", g.col);
+        g.ix = &iit->second;
+        auto uit = t->upd.find(g.col);
+        g.upd = uit == t->upd.end() ? nullptr : &uit->second;
+        static const std::vector<int64_t> none;
+        g.slots = group_slots(g.ix->keys, g.upd ? g.upd->stat_values : none,
+                              g.c->validity != nullptr || (g.upd && g.upd->any_null));
+    }
+    *n1 = gc[0].slots.size();
+    *n2 = n_group_cols > 1 ? gc[1].slots.size() : 1u;
+    if (group_count(*n1, *n2) < 0)
+        return fail(CUBIT_ERR_UNSUPPORTED, "%u x %u groups (at most %d)", *n1, *n2, CUBIT_AGG_MAX_GROUPS);
+    return CUBIT_OK;
+}
+
+// the grouped aggregate's workspace and key staging, on first use
+int ensure_grouped(cubit_ctx* ctx) {
+    if (ctx->gagg) return CUBIT_OK;
+    constexpr size_t kKeyBytes = (size_t)CUBIT_AGG_MAX_GROUP_COLS * CUBIT_AGG_MAX_GROUPS * sizeof(int64_t);
+    if (hipMalloc(&ctx->gkeys_dev, kKeyBytes) != hipSuccess || hipHostMalloc(&ctx->gkeys_host, kKeyBytes) != hipSuccess ||
+        hipEventCreateWithFlags(&ctx->gkeys_ev, hipEventDisableTiming) != hipSuccess ||
+        hipMalloc(&ctx->gagg, kGroupWorkspace * sizeof(int64_t)) != hipSuccess) {
+        if (ctx->gkeys_dev) (void)hipFree(ctx->gkeys_dev);
+        if (ctx->gkeys_host) (void)hipHostFree(ctx->gkeys_host);
+        if (ctx->gkeys_ev) (void)hipEventDestroy(ctx->gkeys_ev);
+        ctx->gkeys_dev = ctx->gkeys_host = nullptr;
+        ctx->gkeys_ev = nullptr;
+        ctx->gagg = nullptr;
+        return fail(CUBIT_ERR_OOM, "grouped aggregate workspace allocation failed");
+    }
+    return CUBIT_OK;
+}
+
+}  // namespace
+
+extern "C" int cubit_table_aggregate_groups(cubit_table* t, const int* group_cols, uint32_t n_group_cols, int64_t* keys,
+                                            uint8_t* key_is_null, uint32_t cap, uint32_t* n_groups) {
+    if (!t || !group_cols || !n_groups) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    GroupCol gc[CUBIT_AGG_MAX_GROUP_COLS];
+    uint32_t n1 = 0, n2 = 1;
+    if (int rc = group_columns(t, group_cols, n_group_cols, gc, &n1, &n2)) return rc;
+    *n_groups = n1 * n2;
+    for (uint32_t g = 0; g < std::min(cap, n1 * n2); ++g) {
+        uint32_t i[2];
+        group_tuple(g, n2, &i[0], &i[1]);
+        for (uint32_t k = 0; k < n_group_cols; ++k) {
+            const bool null = i[k] >= gc[k].slots.keys.size();
+            if (keys) keys[(size_t)g * n_group_cols + k] = null ? 0 : agg_key_value(gc[k].c->type, gc[k].slots.keys[i[k]]);
+            if (key_is_null) key_is_null[(size_t)g * n_group_cols + k] = null ? 1 : 0;
+        }
+    }
+    return CUBIT_OK;
+}
+
+// cubit_table_aggregate per group of one or two EQUALITY-indexed columns: one plan, then either the
+// fused evaluate + aggregate over the value column's slices, a batch of groups per launch, or the
+// plan's decode into scratch, the probes of the value column and the group columns (which apply the
+// visible updates) and a reduction per group. grouped_from_slices (cubit_program.hpp) chooses.
+extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_nodes,
+                                             const cubit_txn* txn, int col, const int* group_cols,
+                                             uint32_t n_group_cols, uint32_t ops, int64_t* d_out, uint32_t cap_groups) {
+    if (!t || !d_out || !group_cols) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    if (n_nodes && !nodes) return fail(CUBIT_ERR_INVALID, "nodes is null");
+    constexpr uint32_t kOps = CUBIT_AGG_SUM | CUBIT_AGG_MIN | CUBIT_AGG_MAX;
+    if (ops & ~(kOps | CUBIT_AGG_FROM_SLICES | CUBIT_AGG_FROM_COLUMN | CUBIT_AGG_NO_ZONEMAP))
+        return fail(CUBIT_ERR_INVALID, "ops %u", ops);
+    const bool force_slices = (ops & CUBIT_AGG_FROM_SLICES) != 0, force_column = (ops & CUBIT_AGG_FROM_COLUMN) != 0;
+    if (force_slices && force_column) return fail(CUBIT_ERR_INVALID, "both paths forced");
+    auto cit = t->cols.find(col);
+    if (cit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column %d not registered", col);
+    const Column& c = cit->second;
+    if ((ops & CUBIT_AGG_SUM) && (type_is_fp(c.type) || c.type == CUBIT_TYPE_VARCHAR || c.dict))
+        return fail(CUBIT_ERR_UNSUPPORTED, "SUM of column %d (type %d): its keys are not linear in the value", col,
+                    c.type);
+    GroupCol gc[CUBIT_AGG_MAX_GROUP_COLS];
+    uint32_t n1 = 0, n2 = 1;
+    if (int rc = group_columns(t, group_cols, n_group_cols, gc, &n1, &n2)) return rc;
+    const uint32_t n_groups = n1 * n2;
+    if (cap_groups < n_groups) return fail(CUBIT_ERR_CAPACITY, "%u groups, room for %u", n_groups, cap_groups);
+    if (int rc = set_device(t->ctx)) return rc;
+    cubit_ctx* ctx = t->ctx;
+    ctx->last_tiles = 0;  // no row ids reach the caller, so no tile directory
+    auto sit = t->sliced.find(col);
+    auto visible = [&](int column) {
+        auto uit = t->upd.find(column);
+        return txn && uit != t->upd.end() && uit->second.any_visible(txn);
+    };
+    bool visible_updates = visible(col);
+    for (uint32_t k = 0; k < n_group_cols; ++k) visible_updates |= visible(gc[k].col);
+    const bool usable = sit != t->sliced.end() && !sit->second.empty && t->use_sliced && !visible_updates;
+    if (force_slices && !usable)
+        return fail(CUBIT_ERR_INVALID, "column %d has no usable bit-sliced index%s", col,
+                    visible_updates ? " (an update record of it or of a group column is visible to the transaction)" : "");
+    t->last_grouped_slices = false;
+    t->last_grouped_groups = n_groups;
+    t->last_grouped_launches = 0;
+    if (n_groups == 0) return CUBIT_OK;
+    // every group starts as six zeros: the kernels write the groups that reach them
+    HIP_CHECK(hipMemsetAsync(d_out, 0, (size_t)n_groups * 6 * sizeof(int64_t), ctx->stream));
+    if (t->n_rows == 0) {  // empty partition
+        t->last_leaves = t->last_passes = 0;
+        t->last_live = t->last_zones = 0;
+        t->last_sliced = 0;
+        return CUBIT_OK;
+    }
+    uint64_t est_rows = t->n_rows;
+    if (usable && !force_slices && !force_column)
+        if (int rc = cubit_table_estimate_rows(t, nodes, n_nodes, &est_rows)) return rc;
+    Emitter em;
+    bool empty = false;
+    std::vector<uint32_t> live;
+    t->last_zones = real_zones(t);
+    t->last_live = 0;
+    if (int rc = plan_program(t, nodes, n_nodes, txn, em, &empty, (ops & CUBIT_AGG_NO_ZONEMAP) ? nullptr : &live))
+        return rc;
+    if (empty) return CUBIT_OK;  // the filter folded to FALSE (or the zonemaps rule out every zone)
+    t->last_live = live.empty() ? t->last_zones : (uint32_t)live.size();
+    const uint64_t live_rows = std::min<uint64_t>(t->n_rows, (uint64_t)t->last_live * kZoneRows);
+    const uint32_t bits = usable ? (uint32_t)sit->second.bvs.size() : 0;
+    if (int rc = ensure_grouped(ctx)) return rc;
+
+    // the slots that have a bitvector: a key's index leaf, and the NULL slot of a nullable column
+    std::vector<GroupLeaf> leaves[CUBIT_AGG_MAX_GROUP_COLS];
+    for (uint32_t k = 0; k < n_group_cols; ++k) {
+        const GroupSlots& s = gc[k].slots;
+        for (uint32_t i = 0; i < s.keys.size(); ++i)
+            if (s.leaf[i] >= 0) leaves[k].push_back({gc[k].ix->bvs[(size_t)s.leaf[i]], false, i});
+        if (s.has_null && gc[k].c->validity) leaves[k].push_back({gc[k].c->validity, true, (uint32_t)s.keys.size()});
+    }
+    const bool two = n_group_cols > 1;
+    const bool minmax = (ops & (CUBIT_AGG_MIN | CUBIT_AGG_MAX)) != 0;
+    const uint32_t row_bits = bits + em.prog.n_leaves + (c.validity ? 1u : 0u);
+    bool swapped = false;
+    const std::vector<GroupBatch> batches =
+        split_group_batches((uint32_t)leaves[0].size(), two ? (uint32_t)leaves[1].size() : 0u, two,
+                            minmax ? kGroupBatchMinMax : kGroupBatchSum, row_bits, &swapped);
+    uint64_t elem_bytes[1 + CUBIT_AGG_MAX_GROUP_COLS] = {type_is32(c.type) ? 4u : 8u, 0, 0};
+    for (uint32_t k = 0; k < n_group_cols; ++k) elem_bytes[1 + k] = type_is32(gc[k].c->type) ? 4 : 8;
+    if (grouped_from_slices(force_slices, force_column, usable, batches.empty() ? row_bits : group_batches_bits(batches, row_bits),
+                            em.prog.n_leaves, live_rows, t->n_rows, est_rows, elem_bytes, 1 + n_group_cols)) {
+        if (t->n_rows >= (1ull << 47))
+            return fail(CUBIT_ERR_INVALID, "%llu rows exceed 2^47", (unsigned long long)t->n_rows);
+        const Index& sx = sit->second;
+        SliceAggArgs g{};
+        g.slices = slice_set(sx);
+        g.n_slices = bits;
+        g.validity = c.validity;
+        EvalArgs a{};
+        a.prog = em.prog;
+        a.n_rows = t->n_rows;
+        a.n_words = (t->n_rows + 63) / 64;
+        a.row_base = t->row_base;
+        a.num_tiles = (uint32_t)((a.n_words + kAggTileWords - 1) / kAggTileWords);
+        if (!live.empty()) {  // zonemap skip: a zone is one tile of the kernel
+            uint32_t n_live = 0;
+            if (int rc = upload_live(ctx, live, 1, &a.live, &n_live)) return rc;
+            a.num_tiles = n_live;
+        }
+        const std::vector<GroupLeaf>& la = leaves[swapped ? 1 : 0];
+        const std::vector<GroupLeaf>& lb = leaves[swapped ? 0 : 1];
+        for (const GroupBatch& b : batches) {
+            GroupAggArgs q{};
+            q.partials = ctx->gagg;
+            q.n1 = b.na;
+            q.n2 = b.nb;
+            for (uint32_t j = 0; j < kGroupBatchSum; ++j) q.group[j] = kNoGroup;
+            for (uint32_t x = 0; x < b.na; ++x) {
+                q.e1[x] = la[b.a0 + x].bv;
+                q.neg1 |= la[b.a0 + x].neg ? 1u << x : 0u;
+            }
+            for (uint32_t y = 0; y < b.nb; ++y) {
+                q.e2[y] = lb[b.b0 + y].bv;
+                q.neg2 |= lb[b.b0 + y].neg ? 1u << y : 0u;
+            }
+            for (uint32_t x = 0; x < b.na; ++x) {
+                if (!two) {
+                    q.group[x] = la[b.a0 + x].slot;
+                    continue;
+                }
+                for (uint32_t y = 0; y < b.nb; ++y) {
+                    const uint32_t sa = la[b.a0 + x].slot, sb = lb[b.b0 + y].slot;
+                    q.group[2 * x + y] = swapped ? group_index(sb, sa, n2) : group_index(sa, sb, n2);
+                }
+            }
+            hipEvent_t e0, e1;
+            if (int rc = timing_events(ctx, e0, e1)) return rc;
+            HIP_CHECK(launch_eval_slice_aggregate_grouped(a, g, q, ops & kOps, c.type, sx.vmin, ctx->n_cus, d_out,
+                                                          ctx->stream, e0, e1));
+            t->last_grouped_launches++;
+        }
+        t->last_grouped_slices = true;
+        t->last_sliced++;
+        return CUBIT_OK;
+    }
+    // the column path: ids, then per probed column (the value column, the group columns) its values,
+    // then their validity words, in context scratch
+    const uint64_t cap = t->n_rows;
+    const uint64_t vwords = (cap + 63) / 64;
+    const uint32_t n_probed = 1 + n_group_cols;
+    if (int rc = ensure_tmp(ctx, (1 + n_probed) * cap + n_probed * vwords)) return rc;
+    int64_t* ids = ctx->tmp_ids;
+    auto values_of = [&](uint32_t k) { return ctx->tmp_ids + (1 + k) * cap; };
+    auto valid_of = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(ctx->tmp_ids + (1 + n_probed) * cap + k * vwords); };
+    uint64_t* count = agg_count_slot(ctx->agg);
+    // (unordered: the decode must not take tmp_ids for an ordering pass)
+    if (int rc = run_eval(ctx, em.prog, t->n_rows, t->row_base, ids, cap, count, nullptr, RunMode::kDecode, true, false,
+                          false, live.empty() ? nullptr : &live, nullptr))
+        return rc;
+    ctx->last_tiles = 0;  // the directory described ids in scratch, not a caller's buffer
+    if (int rc = probe_impl(t, col, txn, ids, count, cap, values_of(0), valid_of(0))) return rc;
+    GroupColArgs ga{};
+    ga.n_cols = n_group_cols;
+    ga.n2 = n2;
+    if (ctx->gkeys_pending) {  // the previous keys' copy must be done before the staging is reused
+        HIP_CHECK(hipEventSynchronize(ctx->gkeys_ev));
+        ctx->gkeys_pending = false;
+    }
+    for (uint32_t k = 0; k < n_group_cols; ++k) {
+        if (int rc = probe_impl(t, gc[k].col, txn, ids, count, cap, values_of(1 + k), valid_of(1 + k))) return rc;
+        const GroupSlots& s = gc[k].slots;
+        std::copy(s.keys.begin(), s.keys.end(), ctx->gkeys_host + (size_t)k * CUBIT_AGG_MAX_GROUPS);
+        ga.v[k] = values_of(1 + k);
+        ga.valid[k] = valid_of(1 + k);
+        ga.keys[k] = ctx->gkeys_dev + (size_t)k * CUBIT_AGG_MAX_GROUPS;
+        ga.n_keys[k] = (uint32_t)s.keys.size();
+        ga.null_slot[k] = s.has_null ? (int32_t)s.keys.size() : -1;
+        ga.type[k] = gc[k].c->type;
+    }
+    HIP_CHECK(hipMemcpyAsync(ctx->gkeys_dev, ctx->gkeys_host,
+                             (size_t)CUBIT_AGG_MAX_GROUP_COLS * CUBIT_AGG_MAX_GROUPS * sizeof(int64_t),
+                             hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipEventRecord(ctx->gkeys_ev, ctx->stream));
+    ctx->gkeys_pending = true;
+    HIP_CHECK(launch_aggregate_arrays_grouped(values_of(0), valid_of(0), ga, n_groups, count, cap, ops & kOps, c.type,
+                                              ctx->gagg, d_out, ctx->stream));
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_last_grouped(cubit_table* t, int* from_slices, uint32_t* n_groups, uint32_t* n_launches) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    if (from_slices) *from_slices = t->last_grouped_slices ? 1 : 0;
+    if (n_groups) *n_groups = t->last_grouped_groups;
+    if (n_launches) *n_launches = t->last_grouped_launches;
     return CUBIT_OK;
 }
 

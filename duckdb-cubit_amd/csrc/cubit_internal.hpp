@@ -227,6 +227,51 @@ hipError_t launch_eval_slice_aggregate(EvalArgs a, const SliceAggArgs& g, uint32
 // (bit i, null = all valid), i < min(*d_count, max_n)
 hipError_t launch_aggregate_arrays(const int64_t* x, const uint64_t* valid, const uint64_t* d_count, uint64_t max_n,
                                    uint32_t ops, int type, int64_t* workspace, int64_t* out, hipStream_t stream);
+// The grouped forms (cubit_table_aggregate_grouped). Either kernel leaves kGroupPartial int64 per
+// group and workgroup in `partials`, group-major ([slot][workgroup]) — {Σ lo, Σ hi, smallest offset,
+// largest offset, valid rows, rows} — and one finishing wave per group combines them as above
+// (six zeros for a group without a row). The workspace (kGroupWorkspace int64, allocated on the
+// context when the first grouped call needs it) holds the column path's CUBIT_AGG_MAX_GROUPS groups ×
+// kGroupColGrid workgroups; the slice path's kGroupBatchSum slots × kAggMaxGrid workgroups fit in it.
+constexpr int kGroupPartial = 6;
+constexpr unsigned kGroupColGrid = 512;
+constexpr uint64_t kGroupWorkspace = (uint64_t)kGroupPartial * CUBIT_AGG_MAX_GROUPS * kGroupColGrid;
+static_assert((uint64_t)kGroupPartial * kGroupBatchSum * kAggMaxGrid <= kGroupWorkspace, "the slice path's partials fit");
+constexpr uint32_t kNoGroup = 0xffffffffu;
+// One launch's rectangle of groups: slot j = a (one group column, n2 = 0) or 2·a + b (two), its
+// rows F ∧ v ∧ e1[a] ∧ e2[b]. A leaf with its neg bit set is a group column's validity, complemented
+// in the kernel (the NULL slot); it is read only below ceil(n_rows / 64) words, as every leaf is.
+struct GroupAggArgs {
+    const uint64_t* e1[kGroupBatchSum];
+    const uint64_t* e2[2];
+    uint32_t n1, n2;
+    uint32_t neg1, neg2;
+    uint32_t group[kGroupBatchSum];  // the group each slot's result goes to (kNoGroup: none)
+    int64_t* partials;
+};
+// a as launch_eval_slice_aggregate's (a.count and a.ticket are not used: each group's rows are
+// counted in its partials); g.workspace is not used. q.n1 ≤ kGroupBatchSum (kGroupBatchMinMax when
+// ops holds MIN or MAX) with one group column, half that with two. out: the whole result, 6 int64
+// per group.
+hipError_t launch_eval_slice_aggregate_grouped(const EvalArgs& a, const SliceAggArgs& g, const GroupAggArgs& q,
+                                               uint32_t ops, int type, int64_t base, int n_cus, int64_t* out,
+                                               hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// The column path's reduction per group: x / xvalid as launch_aggregate_arrays', and per group column
+// its probed values, their validity words, its type, the ascending keys of its non-NULL slots
+// (device) and its NULL slot (-1: none). A row whose group value is in no slot counts nowhere.
+struct GroupColArgs {
+    const int64_t* v[2];
+    const uint64_t* valid[2];
+    const int64_t* keys[2];
+    uint32_t n_keys[2];
+    int32_t null_slot[2];
+    int type[2];
+    uint32_t n_cols;
+    uint32_t n2;  // slots of the second column (1 with one column)
+};
+hipError_t launch_aggregate_arrays_grouped(const int64_t* x, const uint64_t* valid, const GroupColArgs& gc,
+                                           uint32_t n_groups, const uint64_t* d_count, uint64_t max_n, uint32_t ops,
+                                           int type, int64_t* partials, int64_t* out, hipStream_t stream);
 // after a merge: every 64-row word holding one of the m merged rows (ascending) sliced again from
 // the column as it stands
 hipError_t launch_bitslice_reslice(const int64_t* rows, uint64_t m, const void* col, int type, const uint64_t* validity,

@@ -2468,6 +2468,381 @@ __global__ __launch_bounds__(64) void aggregate_finish_kernel(const int64_t* __r
     }
 }
 
+// GROUP BY: eval_slice_aggregate over a batch of groups per launch. Each group is the AND of one
+// equality bitvector per group column, so the tile walk, the program evaluation and the slice stream
+// are eval_slice_aggregate's, read once for the whole batch, and per pair of words the batch's group
+// leaves are loaded once (16 bytes each) and every group's rows formed in registers as
+// m = F ∧ E1_a ∧ E2_b (then ∧ v for the valid rows). A leaf flagged in neg is a group column's
+// validity: its complement under F (tail_mask has cleared the bits past n_rows) is the NULL group.
+// Per chunk of slices every group adds its Horner popcount sum to its own 128-bit accumulator, and
+// with MINMAX runs its own candidate ripple. A pair whose F is zero across the wave loads nothing
+// more; one whose groups' valid rows are all zero skips the slices; a group whose mask is zero across
+// the wave skips its arithmetic (wave-uniform branches). The batch is NG = kGroupBatchSum groups, or
+// kGroupBatchMinMax with MINMAX (the ripple keeps 16 more registers per group): NG × 1 leaves with one
+// group column, NG/2 × 2 with TWO. Each group's rows are counted in its partials, so the kernel takes
+// no ticket. Traffic: (b + K [+ 1] + the launch's group leaves)·n/8 bytes over the live zones.
+template <int THREADS>
+__device__ __forceinline__ u64x2 load_group_leaf(const uint64_t* bv, bool neg, bool whole, uint64_t tile_word0, int p,
+                                                 int t, uint64_t n_words) {
+    u64x2 e;
+    if (whole) {  // uniform: the whole tile lies below the last word
+        e = reinterpret_cast<const u64x2*>(bv + tile_word0)[p * THREADS + t];
+    } else {  // the tile holding the last word: nothing at or past n_words is read
+        const uint64_t gw = word_index<THREADS>(tile_word0, 2 * p, t);
+        e.x = gw < n_words ? bv[gw] : 0ull;
+        e.y = gw + 1 < n_words ? bv[gw + 1] : 0ull;
+    }
+    return neg ? ~e : e;
+}
+
+// One chunk of CNT slices from `top` down for every live group. GUARD: the chunk may reach above the
+// index's slices (the slice count rounded up to the chunk), and a slice that does not exist reads as
+// zero: it adds nothing to a sum, leaves a non-empty candidate set as it is (bit 0 of the offset) and
+// makes an empty word's MIN offset larger still.
+template <int NG, bool MINMAX, int CNT, bool GUARD>
+__device__ __forceinline__ void agg_chunk_grouped(const SliceSet& sl, int n_slices, int top, uint64_t pi, uint32_t live,
+                                                  const u64x2 (&m)[NG], U128 (&acc)[NG], u64x2 (&cmin)[NG],
+                                                  u64x2 (&cmax)[NG], u64x2 (&omin)[NG], u64x2 (&omax)[NG]) {
+    u64x2 w[CNT];
+#pragma unroll
+    for (int j = 0; j < CNT; ++j) {
+        if (GUARD && top - j >= n_slices) w[j] = u64x2{0ull, 0ull};
+        else w[j] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(sl.s[top - j]) + pi);
+    }
+#pragma unroll
+    for (int q = 0; q < NG; ++q) {
+        if (!((live >> q) & 1u)) continue;  // no valid row of this group in the wave's 128 words
+        uint32_t local = 0;  // Horner from the chunk's top slice: ≤ 128·(2^CNT - 1)
+#pragma unroll
+        for (int j = 0; j < CNT; ++j)
+            local = (local << 1) + (uint32_t)(__popcll(m[q].x & w[j].x) + __popcll(m[q].y & w[j].y));
+        acc[q] = u128_add(acc[q], u128_shl(local, (uint32_t)(top - CNT + 1)));
+        if (MINMAX) {
+#pragma unroll
+            for (int j = 0; j < CNT; ++j) {
+                const u64x2 tn = cmin[q] & ~w[j], tx = cmax[q] & w[j];
+                const bool nx = tn.x != 0, ny = tn.y != 0, xx = tx.x != 0, xy = tx.y != 0;
+                cmin[q].x = nx ? tn.x : cmin[q].x;
+                cmin[q].y = ny ? tn.y : cmin[q].y;
+                cmax[q].x = xx ? tx.x : cmax[q].x;
+                cmax[q].y = xy ? tx.y : cmax[q].y;
+                omin[q].x = (omin[q].x << 1) | (nx ? 0ull : 1ull);
+                omin[q].y = (omin[q].y << 1) | (ny ? 0ull : 1ull);
+                omax[q].x = (omax[q].x << 1) | (xx ? 1ull : 0ull);
+                omax[q].y = (omax[q].y << 1) | (xy ? 1ull : 0ull);
+            }
+        }
+    }
+}
+
+template <int K, int FORM, bool TWO, bool MINMAX>
+__global__ __launch_bounds__(512, 2) void eval_slice_aggregate_grouped(EvalArgs a, SliceAggArgs g, GroupAggArgs q) {
+    constexpr int THREADS = 512, PAIRS = 2, NW = 4;
+    constexpr uint64_t TILE_WORDS = (uint64_t)THREADS * NW;
+    static_assert(TILE_WORDS == kAggTileWords, "a tile is one zone");
+    constexpr int NWAVES = THREADS / 64;
+    constexpr int NG = MINMAX ? (int)kGroupBatchMinMax : (int)kGroupBatchSum;
+    constexpr int NA = TWO ? NG / 2 : NG;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    U128 acc[NG];
+    uint64_t mn[NG], mx[NG], c_rows[NG], c_valid[NG];
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        acc[j] = U128{0, 0};
+        mn[j] = ~0ull;
+        mx[j] = 0;
+        c_rows[j] = c_valid[j] = 0;
+    }
+    const uint32_t n_idx = a.num_tiles;
+    for (uint32_t i = blockIdx.x; i < n_idx; i += gridDim.x) {
+        const uint64_t tile_word0 = (uint64_t)tile_at(a, i) * TILE_WORDS;
+        uint64_t r[NW];
+        if constexpr (K > 0) {
+            u64x2 v[K][PAIRS];
+            load_tile<K, PAIRS, THREADS>(a, tile_word0, t, v);
+            eval_words<K, NW, FORM>(a.prog, v, r);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) r[j] = ~0ull;
+        }
+        tail_mask<NW, THREADS>(a, tile_word0, t, r);
+        const bool whole = tile_word0 + TILE_WORDS <= a.n_words;
+        static_assert(PAIRS == 2, "the pair loop selects between two pairs");
+        // one pair at a time (not unrolled: both pairs' masks and slices in flight do not fit the
+        // register file; p is uniform, so the selects are scalar)
+#pragma unroll 1
+        for (int p = 0; p < PAIRS; ++p) {
+            u64x2 f;
+            f.x = p ? r[2] : r[0];
+            f.y = p ? r[3] : r[1];
+            if (__ballot((f.x | f.y) != 0) == 0) continue;  // no qualifying row in the wave's 128 words
+            u64x2 m[NG];
+            if (TWO) {
+                u64x2 eb[2];
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    eb[b] = u64x2{0ull, 0ull};
+                    if ((uint32_t)b < q.n2)
+                        eb[b] = load_group_leaf<THREADS>(q.e2[b], (q.neg2 >> b) & 1u, whole, tile_word0, p, t, a.n_words);
+                }
+#pragma unroll
+                for (int x = 0; x < NA; ++x) {
+                    u64x2 ea = {0ull, 0ull};
+                    if ((uint32_t)x < q.n1)
+                        ea = f & load_group_leaf<THREADS>(q.e1[x], (q.neg1 >> x) & 1u, whole, tile_word0, p, t, a.n_words);
+                    m[2 * x] = ea & eb[0];
+                    m[2 * x + 1] = ea & eb[1];
+                }
+            } else {
+#pragma unroll
+                for (int x = 0; x < NA; ++x) {
+                    m[x] = u64x2{0ull, 0ull};
+                    if ((uint32_t)x < q.n1)
+                        m[x] = f & load_group_leaf<THREADS>(q.e1[x], (q.neg1 >> x) & 1u, whole, tile_word0, p, t, a.n_words);
+                }
+            }
+            if (g.validity) {
+                const u64x2 vv = load_group_leaf<THREADS>(g.validity, false, whole, tile_word0, p, t, a.n_words);
+#pragma unroll
+                for (int j = 0; j < NG; ++j) {
+                    c_rows[j] += (uint64_t)(__popcll(m[j].x) + __popcll(m[j].y));
+                    m[j] &= vv;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NG; ++j) c_rows[j] += (uint64_t)(__popcll(m[j].x) + __popcll(m[j].y));
+            }
+            uint32_t live = 0;
+#pragma unroll
+            for (int j = 0; j < NG; ++j) {
+                c_valid[j] += (uint64_t)(__popcll(m[j].x) + __popcll(m[j].y));
+                if (__ballot((m[j].x | m[j].y) != 0) != 0) live |= 1u << j;
+            }
+            if (live == 0) continue;
+            const uint64_t pi = (tile_word0 >> 1) + (uint64_t)(p * THREADS + t);
+            u64x2 cmin[NG], cmax[NG], omin[NG], omax[NG];
+#pragma unroll
+            for (int j = 0; j < NG; ++j) {
+                cmin[j] = cmax[j] = m[j];
+                omin[j] = omax[j] = u64x2{0ull, 0ull};
+            }
+            // the top slices that fill no chunk of 4 as one guarded chunk, then whole chunks (chunks of
+            // 8, as the ungrouped kernel takes them, spill beside a batch of masks and accumulators)
+            const int ns = (int)g.n_slices, rem = ns & 3;
+            int top = ns - rem - 1;
+            if (rem > 0)
+                agg_chunk_grouped<NG, MINMAX, 4, true>(g.slices, ns, top + 4, pi, live, m, acc, cmin, cmax, omin, omax);
+#pragma unroll 1
+            for (; top >= 3; top -= 4)
+                agg_chunk_grouped<NG, MINMAX, 4, false>(g.slices, ns, top, pi, live, m, acc, cmin, cmax, omin, omax);
+            if (MINMAX) {
+#pragma unroll
+                for (int j = 0; j < NG; ++j) {
+                    if (!((live >> j) & 1u)) continue;
+                    // (a word of the pair without a row of the group gives 2^b - 1 / 0: never below /
+                    // above another word's offset)
+                    const uint64_t lo = omin[j].x < omin[j].y ? omin[j].x : omin[j].y;
+                    const uint64_t hi = omax[j].x > omax[j].y ? omax[j].x : omax[j].y;
+                    mn[j] = lo < mn[j] ? lo : mn[j];
+                    mx[j] = hi > mx[j] ? hi : mx[j];
+                }
+            }
+        }
+    }
+    // wave, then workgroup, per group: exact integer adds and unsigned min / max, so any order gives
+    // the same
+    __shared__ uint64_t s_part[NWAVES][NG][kGroupPartial];
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            U128 o;
+            o.lo = __shfl_xor(acc[j].lo, d, 64);
+            o.hi = __shfl_xor(acc[j].hi, d, 64);
+            acc[j] = u128_add(acc[j], o);
+            const uint64_t omn = __shfl_xor(mn[j], d, 64), omx = __shfl_xor(mx[j], d, 64);
+            mn[j] = omn < mn[j] ? omn : mn[j];
+            mx[j] = omx > mx[j] ? omx : mx[j];
+            c_rows[j] += __shfl_xor(c_rows[j], d, 64);
+            c_valid[j] += __shfl_xor(c_valid[j], d, 64);
+        }
+        if (lane == 0) {
+            s_part[wave][j][0] = acc[j].lo;
+            s_part[wave][j][1] = acc[j].hi;
+            s_part[wave][j][2] = mn[j];
+            s_part[wave][j][3] = mx[j];
+            s_part[wave][j][4] = c_valid[j];
+            s_part[wave][j][5] = c_rows[j];
+        }
+    }
+    __syncthreads();
+    if (t < NG) {
+        U128 s{0, 0};
+        uint64_t lo = ~0ull, hi = 0, cv = 0, cr = 0;
+        for (int w = 0; w < NWAVES; ++w) {
+            s = u128_add(s, U128{s_part[w][t][0], s_part[w][t][1]});
+            lo = s_part[w][t][2] < lo ? s_part[w][t][2] : lo;
+            hi = s_part[w][t][3] > hi ? s_part[w][t][3] : hi;
+            cv += s_part[w][t][4];
+            cr += s_part[w][t][5];
+        }
+        int64_t* part = q.partials + ((uint64_t)t * gridDim.x + blockIdx.x) * kGroupPartial;
+        part[0] = (int64_t)s.lo;
+        part[1] = (int64_t)s.hi;
+        part[2] = (int64_t)lo;
+        part[3] = (int64_t)hi;
+        part[4] = (int64_t)cv;
+        part[5] = (int64_t)cr;
+    }
+}
+
+// The column path per group: x / valid as aggregate_arrays_kernel's, and per group column the probed
+// value and its validity. Each row's group values map to slots by binary search over the columns'
+// ascending slot keys (a NULL value: the column's NULL slot), and the row is accumulated into its
+// group in LDS: the value's two 32-bit halves go to two 64-bit LDS sums (the high half signed, or
+// unsigned for UINT64), which cannot wrap within kGroupFlushIters iterations of 256 rows; every so
+// many iterations, and at the end, a thread per group folds them into the group's 128-bit sum. Min /
+// max go through the comparison key as an unsigned offset from INT64_MIN, as above. The partials
+// are the grouped slice kernel's.
+constexpr uint32_t kGroupFlushIters = 64;
+__device__ __forceinline__ int group_slot_of(const GroupColArgs& gc, int c, uint64_t i) {
+    if (gc.valid[c] && !((gc.valid[c][i >> 6] >> (i & 63)) & 1ull)) return gc.null_slot[c];
+    const int64_t key = value_key(gc.type[c], gc.v[c][i]);
+    const int64_t* keys = gc.keys[c];
+    uint32_t lo = 0, hi = gc.n_keys[c];
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (keys[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < gc.n_keys[c] && keys[lo] == key ? (int)lo : -1;
+}
+
+__global__ __launch_bounds__(256) void aggregate_arrays_grouped_kernel(const int64_t* __restrict__ x,
+                                                                       const uint64_t* __restrict__ valid,
+                                                                       GroupColArgs gc, uint32_t n_groups,
+                                                                       const uint64_t* __restrict__ d_count,
+                                                                       uint64_t max_n, uint32_t ops, int type,
+                                                                       int64_t* __restrict__ partials) {
+    // per group: {Σ low halves, Σ high halves, sum lo, sum hi, min, max, valid rows, rows}
+    __shared__ unsigned long long s_acc[CUBIT_AGG_MAX_GROUPS][8];
+    const uint64_t n = min(*d_count, max_n);
+    const bool uns = type == kTypeUInt64;
+    for (uint32_t q = threadIdx.x; q < n_groups; q += blockDim.x) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s_acc[q][k] = k == 4 ? ~0ull : 0ull;
+    }
+    __syncthreads();
+    auto fold = [&]() {
+        for (uint32_t q = threadIdx.x; q < n_groups; q += blockDim.x) {
+            const uint64_t l = s_acc[q][0], h = s_acc[q][1];
+            // Σ = l + h·2^32, h sign-extended unless the column is unsigned
+            const U128 hh{h << 32, uns ? h >> 32 : (uint64_t)((int64_t)h >> 32)};
+            const U128 s = u128_add(U128{s_acc[q][2], s_acc[q][3]}, u128_add(U128{l, 0}, hh));
+            s_acc[q][0] = s_acc[q][1] = 0;
+            s_acc[q][2] = s.lo;
+            s_acc[q][3] = s.hi;
+        }
+    };
+    uint32_t iters = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        if (i < n) {
+            const int s1 = group_slot_of(gc, 0, i);
+            const int s2 = gc.n_cols > 1 ? group_slot_of(gc, 1, i) : 0;
+            if (s1 >= 0 && s2 >= 0) {
+                unsigned long long* acc = s_acc[(uint32_t)s1 * gc.n2 + (uint32_t)s2];
+                atomicAdd(&acc[7], 1ull);
+                if (!valid || ((valid[i >> 6] >> (i & 63)) & 1ull)) {
+                    const int64_t v = x[i];
+                    atomicAdd(&acc[6], 1ull);
+                    if (ops & kAggSum) {
+                        atomicAdd(&acc[0], (unsigned long long)(uint32_t)v);
+                        atomicAdd(&acc[1], uns ? (unsigned long long)((uint64_t)v >> 32) : (unsigned long long)(v >> 32));
+                    }
+                    const unsigned long long off = (uint64_t)value_key(type, v) ^ 0x8000000000000000ull;
+                    atomicMin(&acc[4], off);
+                    atomicMax(&acc[5], off);
+                }
+            }
+        }
+        if (++iters == kGroupFlushIters) {  // uniform: the loop bounds are the workgroup's
+            __syncthreads();
+            fold();
+            __syncthreads();
+            iters = 0;
+        }
+    }
+    __syncthreads();
+    fold();
+    for (uint32_t q = threadIdx.x; q < n_groups; q += blockDim.x) {
+        int64_t* part = partials + ((uint64_t)q * gridDim.x + blockIdx.x) * kGroupPartial;
+        part[0] = (int64_t)s_acc[q][2];
+        part[1] = (int64_t)s_acc[q][3];
+        part[2] = (int64_t)s_acc[q][4];
+        part[3] = (int64_t)s_acc[q][5];
+        part[4] = (int64_t)s_acc[q][6];
+        part[5] = (int64_t)s_acc[q][7];
+    }
+}
+
+// One wave per group (slot) combines the workgroups' partials as aggregate_finish_kernel does and
+// writes the group's six result slots; a group without a qualifying row gets six zeros, one whose
+// rows are all NULL its count_rows alone. group: the group of each slot (kNoGroup: none), or null
+// when slot = group.
+__global__ __launch_bounds__(64) void aggregate_grouped_finish_kernel(const int64_t* __restrict__ partials, int nblocks,
+                                                                      GroupAggArgs q, int identity, uint32_t ops,
+                                                                      int type, int64_t base, int from_slices,
+                                                                      int64_t* __restrict__ out) {
+    const int lane = threadIdx.x;
+    const uint32_t slot = blockIdx.x;
+    const uint32_t group = identity ? slot : q.group[slot < kGroupBatchSum ? slot : 0];
+    if (group == kNoGroup) return;
+    U128 acc{0, 0};
+    uint64_t mn = ~0ull, mx = 0, cv = 0, cr = 0;
+    for (int b = lane; b < nblocks; b += 64) {
+        const int64_t* part = partials + ((uint64_t)slot * nblocks + b) * kGroupPartial;
+        acc = u128_add(acc, U128{(uint64_t)part[0], (uint64_t)part[1]});
+        mn = (uint64_t)part[2] < mn ? (uint64_t)part[2] : mn;
+        mx = (uint64_t)part[3] > mx ? (uint64_t)part[3] : mx;
+        cv += (uint64_t)part[4];
+        cr += (uint64_t)part[5];
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        U128 o;
+        o.lo = __shfl_xor(acc.lo, d, 64);
+        o.hi = __shfl_xor(acc.hi, d, 64);
+        acc = u128_add(acc, o);
+        const uint64_t omn = __shfl_xor(mn, d, 64), omx = __shfl_xor(mx, d, 64);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+        cv += __shfl_xor(cv, d, 64);
+        cr += __shfl_xor(cr, d, 64);
+    }
+    if (lane == 0) {
+        int64_t r[4] = {0, 0, 0, 0};
+        if (cv != 0) {
+            if (from_slices) {
+                slice_agg_combine(type, base, cv, acc, mn, mx, ops, r);
+            } else {
+                slice_agg_combine(type, INT64_MIN, cv, U128{0, 0}, mn, mx, ops & ~kAggSum, r);
+                if (ops & kAggSum) {
+                    r[0] = (int64_t)acc.lo;
+                    r[1] = (int64_t)acc.hi;
+                }
+            }
+        }
+        int64_t* o = out + (uint64_t)group * 6;
+        o[0] = r[0];
+        o[1] = r[1];
+        o[2] = r[2];
+        o[3] = r[3];
+        o[4] = (int64_t)cv;
+        o[5] = (int64_t)cr;
+    }
+}
+
 // ------------------------------------------------------------------ index build: column stats
 
 // min / max / any-valid of a column (the statistics an index build needs; the reference
@@ -4231,6 +4606,60 @@ hipError_t launch_aggregate_arrays(const int64_t* x, const uint64_t* valid, cons
                        workspace);
     hipLaunchKernelGGL(aggregate_finish_kernel, dim3(1), dim3(64), 0, stream, workspace, (int)grid, ops, type,
                        (int64_t)0, 0, out);
+    return hipGetLastError();
+}
+
+// the grouped slice kernel's forms: one or two group columns, with or without the MIN / MAX ripple
+// (a MIN / MAX call computes the sums too and the finishing wave drops them)
+template <int K, int FORM>
+void launch_slice_aggregate_grouped_kf(const EvalArgs& a, const SliceAggArgs& g, const GroupAggArgs& q, bool minmax,
+                                       unsigned grid, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    const bool two = q.n2 != 0;
+#define CUBIT_GROUPED(TWO, MM)                                                                                       \
+    hipExtLaunchKernelGGL((eval_slice_aggregate_grouped<K, FORM, TWO, MM>), dim3(grid), dim3(512), 0, s, e0, e1, 0, a, g, q)
+    if (two && minmax) CUBIT_GROUPED(true, true);
+    else if (two) CUBIT_GROUPED(true, false);
+    else if (minmax) CUBIT_GROUPED(false, true);
+    else CUBIT_GROUPED(false, false);
+#undef CUBIT_GROUPED
+}
+
+hipError_t launch_eval_slice_aggregate_grouped(const EvalArgs& a, const SliceAggArgs& g, const GroupAggArgs& q,
+                                               uint32_t ops, int type, int64_t base, int n_cus, int64_t* out,
+                                               hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+    const bool minmax = (ops & (kAggMin | kAggMax)) != 0;
+    const uint32_t limit = minmax ? kGroupBatchMinMax : kGroupBatchSum;
+    if (g.n_slices > kMaxSlices || a.num_tiles == 0 || !q.partials || q.n2 > 2 || q.n1 == 0 ||
+        q.n1 > (q.n2 ? limit / 2 : limit))
+        return hipErrorInvalidValue;
+    // persistent grid: one 512-thread workgroup per CU at the kernel's register count
+    const unsigned grid = std::max(1u, std::min<unsigned>(a.num_tiles, std::min<unsigned>((unsigned)n_cus, kAggMaxGrid)));
+    hipError_t e = hipSuccess;
+    if (a.prog.n_leaves == 0)
+        launch_slice_aggregate_grouped_kf<0, FORM_CONJ>(a, g, q, minmax, grid, stream, ev0, ev1);
+    else
+        e = dispatch_k_form(a.prog, [&](auto k, auto form) {
+            launch_slice_aggregate_grouped_kf<k.value, form.value>(a, g, q, minmax, grid, stream, ev0, ev1);
+        });
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(aggregate_grouped_finish_kernel, dim3(limit), dim3(64), 0, stream, q.partials, (int)grid, q, 0, ops,
+                       type, base, 1, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_aggregate_arrays_grouped(const int64_t* x, const uint64_t* valid, const GroupColArgs& gc,
+                                           uint32_t n_groups, const uint64_t* d_count, uint64_t max_n, uint32_t ops,
+                                           int type, int64_t* partials, int64_t* out, hipStream_t stream) {
+    if (n_groups == 0 || n_groups > CUBIT_AGG_MAX_GROUPS || !partials) return hipErrorInvalidValue;
+    // a workgroup takes kGroupFlushIters iterations of 256 rows before the grid grows
+    const unsigned grid = (unsigned)std::max<uint64_t>(
+        1, std::min<uint64_t>((max_n + 256ull * kGroupFlushIters - 1) / (256ull * kGroupFlushIters), kGroupColGrid));
+    hipLaunchKernelGGL(aggregate_arrays_grouped_kernel, dim3(grid), dim3(256), 0, stream, x, valid, gc, n_groups, d_count,
+                       max_n, ops, type, partials);
+    GroupAggArgs none{};
+    hipLaunchKernelGGL(aggregate_grouped_finish_kernel, dim3(n_groups), dim3(64), 0, stream, partials, (int)grid, none, 1,
+                       ops, type, (int64_t)0, 0, out);
     return hipGetLastError();
 }
 

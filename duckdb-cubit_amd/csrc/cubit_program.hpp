@@ -220,6 +220,112 @@ inline bool aggregate_from_slices(bool force_slices, bool force_column, bool usa
     return slices <= column;
 }
 
+// ---- grouped aggregates (cubit_table_aggregate_grouped): GROUP BY one or two columns that carry an
+// every-value EQUALITY index, so each group is the AND of one bitvector per group column.
+//
+// The slots of a group column, ascending: the index's keys, the values its update records carry that
+// are no key (an MVCC update may move a row to a value the index has never seen; such a slot has no
+// bitvector and can have rows on the column path only), then one NULL slot when the column is
+// nullable or a record sets it NULL. Keys are comparison keys (value_key), as Index::keys holds them.
+struct GroupSlots {
+    std::vector<int64_t> keys;  // the non-NULL slots' keys, ascending and distinct
+    std::vector<int32_t> leaf;  // parallel: the key's position in the index (its bitvector), -1 = none
+    bool has_null = false;      // the NULL slot, last
+    uint32_t size() const { return (uint32_t)keys.size() + (has_null ? 1u : 0u); }
+};
+// index_keys and update_values: ascending and distinct, each on its own
+inline GroupSlots group_slots(const std::vector<int64_t>& index_keys, const std::vector<int64_t>& update_values,
+                              bool null_slot) {
+    GroupSlots s;
+    s.has_null = null_slot;
+    size_t i = 0, j = 0;
+    while (i < index_keys.size() || j < update_values.size()) {
+        if (j == update_values.size() || (i < index_keys.size() && index_keys[i] <= update_values[j])) {
+            if (j < update_values.size() && update_values[j] == index_keys[i]) ++j;
+            s.keys.push_back(index_keys[i]);
+            s.leaf.push_back((int32_t)i++);
+        } else {
+            s.keys.push_back(update_values[j++]);
+            s.leaf.push_back(-1);
+        }
+    }
+    return s;
+}
+// Group g = i1·n2 + i2 over the slots of the two columns (n2 = 1 with one column).
+inline uint32_t group_index(uint32_t i1, uint32_t i2, uint32_t n2) { return i1 * n2 + i2; }
+inline void group_tuple(uint32_t g, uint32_t n2, uint32_t* i1, uint32_t* i2) {
+    *i1 = g / n2;
+    *i2 = g % n2;
+}
+// n1·n2 when it is at most CUBIT_AGG_MAX_GROUPS, else -1 (n2 = 1 with one column)
+inline int64_t group_count(uint32_t n1, uint32_t n2) {
+    const uint64_t n = (uint64_t)n1 * n2;
+    return n <= CUBIT_AGG_MAX_GROUPS ? (int64_t)n : -1;
+}
+
+// One launch of eval_slice_aggregate_grouped takes a rectangle of groups: na leaves of the first
+// list from a0 on × nb leaves of the second from b0 on (nb = 0: one group column, nothing loaded for
+// a second). The kernel's rectangles are `limit` × 1 for one column and limit/2 × 2 for two, either
+// column on the side of 2 (`swapped`: the first list is the second group column's).
+constexpr uint32_t kGroupBatchSum = 8;     // groups per launch, SUM and the counts
+constexpr uint32_t kGroupBatchMinMax = 4;  // with MIN / MAX (the ripple state is per group)
+struct GroupBatch {
+    uint32_t a0, na, b0, nb;
+};
+inline std::vector<GroupBatch> group_batches_of(uint32_t na_all, uint32_t nb_all, bool two, uint32_t limit) {
+    std::vector<GroupBatch> out;
+    const uint32_t A = two ? limit / 2 : limit, B = two ? 2u : 0u;
+    if (!two) {
+        for (uint32_t a = 0; a < na_all; a += A) out.push_back({a, std::min(A, na_all - a), 0u, 0u});
+        return out;
+    }
+    for (uint32_t a = 0; a < na_all; a += A)
+        for (uint32_t b = 0; b < nb_all; b += B) out.push_back({a, std::min(A, na_all - a), b, std::min(B, nb_all - b)});
+    return out;
+}
+// bytes per row of a set of launches, in eighths: each reads the row's bits (the slices, the program
+// leaves, the validity) and its own group leaves
+inline uint64_t group_batches_bits(const std::vector<GroupBatch>& bs, uint32_t row_bits) {
+    uint64_t bits = 0;
+    for (const GroupBatch& b : bs) bits += (uint64_t)row_bits + b.na + b.nb;
+    return bits;
+}
+// The split that reads fewer bytes (n1 / n2: the leaves of the first / second group column, n2 = 0
+// with one column; row_bits = b + K + nullable). Every pair of leaves lands in exactly one batch.
+inline std::vector<GroupBatch> split_group_batches(uint32_t n1, uint32_t n2, bool two, uint32_t limit, uint32_t row_bits,
+                                                   bool* swapped) {
+    *swapped = false;
+    if (!two) return group_batches_of(n1, 0, false, limit);
+    std::vector<GroupBatch> plain = group_batches_of(n1, n2, true, limit);
+    std::vector<GroupBatch> swap = group_batches_of(n2, n1, true, limit);
+    if (group_batches_bits(swap, row_bits) < group_batches_bits(plain, row_bits)) {
+        *swapped = true;
+        return swap;
+    }
+    return plain;
+}
+
+// Which path cubit_table_aggregate_grouped takes: aggregate_from_slices extended by bytes alone.
+//   slices: each launch reads (b + K + nullable + its group leaves)/8 bytes per live row:
+//           slice_bits = that sum over the launches (group_batches_bits);
+//   column: the scan reads K/8 bytes per live row; per estimated qualifying row the id is written and
+//           read (16 bytes), and for the value column and each group column the probed value and its
+//           validity are written and read (16 bytes) and the gather moves one 128-byte line, but
+//           never more lines than that column has (elem_bytes: the value column's, then each group
+//           column's).
+// With no group column and one launch without group leaves this is aggregate_from_slices.
+inline bool grouped_from_slices(bool force_slices, bool force_column, bool usable, uint64_t slice_bits, uint32_t k_leaves,
+                                uint64_t live_rows, uint64_t rows, uint64_t est_rows, const uint64_t* elem_bytes,
+                                uint32_t n_probed) {
+    if (force_column || !usable) return false;
+    if (force_slices) return true;
+    const double slices = (double)slice_bits / 8.0 * (double)live_rows;
+    double column = (double)k_leaves / 8.0 * (double)live_rows + 16.0 * (double)est_rows;
+    for (uint32_t i = 0; i < n_probed; ++i)
+        column += 16.0 * (double)est_rows + std::min(128.0 * (double)est_rows, (double)elem_bytes[i] * (double)rows);
+    return slices <= column;
+}
+
 // One past the last node of the subtree rooted at node i of a prefix-order node array, or -1 when
 // the array ends inside it. A negative child count reads as none.
 inline int filter_subtree_end(const cubit_filter_node* nodes, uint32_t n_nodes, uint32_t i) {

@@ -58,6 +58,7 @@ SUM_PLAIN_A = 8
 AGG_SUM, AGG_MIN, AGG_MAX = 1, 2, 4
 AGG_ALL = AGG_SUM | AGG_MIN | AGG_MAX
 AGG_FROM_SLICES, AGG_FROM_COLUMN, AGG_NO_ZONEMAP = 16, 32, 64
+AGG_MAX_GROUP_COLS, AGG_MAX_GROUPS = 2, 256
 OP_AND, OP_OR, OP_ANDNOT = -1, -2, -3
 SCAN_COUNT_ONLY = 1
 SCAN_ORDERED = 2
@@ -198,6 +199,9 @@ GPU_SIGNATURES = {
     "cubit_table_last_sum_packed": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "cubit_table_aggregate": (C.c_int, [_P, _P, _U32, _P, C.c_int, _U32, _P]),
     "cubit_table_last_aggregate": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "cubit_table_aggregate_groups": (C.c_int, [_P, _P, _U32, _P, _P, _U32, C.POINTER(_U32)]),
+    "cubit_table_aggregate_grouped": (C.c_int, [_P, _P, _U32, _P, C.c_int, _P, _U32, _U32, _P, _U32]),
+    "cubit_table_last_grouped": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(_U32), C.POINTER(_U32)]),
     "cubit_bitslice_aggregate": (C.c_int, [_P, _P, _U32, _P, _P, _U64, C.c_int, _I64, _U32, _P]),
     "cubit_table_column_data": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int)]),
     "cubit_table_set_inserts": (C.c_int, [_P, _P, _P, _P, _U64]),

@@ -249,6 +249,7 @@ class CubitTable:
         ctx._tables.add(self)
         self.types: Dict[int, int] = {}
         self.huge: Dict[int, bool] = {}  # HUGEINT (True) / UHUGEINT (False) dictionary columns
+        self.dicts: Dict[int, "Dictionary"] = {}  # the dictionary of each column add_string_column registered
         self._keep = []
 
     def add_column(self, col: int, data: np.ndarray, validity: Optional[np.ndarray] = None) -> None:
@@ -340,6 +341,7 @@ class CubitTable:
                                                      vw.ctypes.data if vw is not None else None, 0))
         self.types[col] = L.TYPE_VARCHAR
         self._keep.append(d)
+        self.dicts[col] = d
         return d
 
     def add_huge_column(self, col: int, values, signed: bool = True,
@@ -654,6 +656,88 @@ class CubitTable:
         v = C.c_int()
         L.check(self.lib.cubit_table_last_aggregate(self.handle, C.byref(v)))
         return bool(v.value)
+
+    def _group_cols(self, by):
+        cols = [int(by)] if isinstance(by, (int, np.integer)) else [int(c) for c in by]
+        return cols, (C.c_int * max(len(cols), 1))(*cols)
+
+    def aggregate_groups(self, by):
+        """The groups of aggregate_by(…, by) in their numbering: a list of key tuples, one entry per
+        group column, None for NULL. Keys are in column_statistics' form; a column registered
+        with add_string_column / add_huge_column gives its dictionary's entries (bytes) / Python
+        ints. `by`: one column or a sequence of one or two, each with an every-value EQUALITY index."""
+        from cubit_amd.filters import value128
+
+        cols, arr = self._group_cols(by)
+        n = C.c_uint32()
+        L.check(self.lib.cubit_table_aggregate_groups(self.handle, arr, len(cols), None, None, 0, C.byref(n)))
+        ng = int(n.value)
+        keys = np.zeros(max(ng * len(cols), 1), dtype=np.int64)
+        nulls = np.zeros(max(ng * len(cols), 1), dtype=np.uint8)
+        L.check(self.lib.cubit_table_aggregate_groups(self.handle, arr, len(cols), keys.ctypes.data, nulls.ctypes.data,
+                                                      ng, C.byref(n)))
+
+        def key_of(c, k, null):
+            if null:
+                return None
+            if c in self.dicts:
+                e = self.dicts[c].entry(k)
+                return value128(e, self.huge[c]) if c in self.huge else e
+            if self.types.get(c) == L.TYPE_UINT64:
+                return k & (2 ** 64 - 1)
+            return k
+
+        return [tuple(key_of(c, int(keys[g * len(cols) + j]), bool(nulls[g * len(cols) + j]))
+                      for j, c in enumerate(cols)) for g in range(ng)]
+
+    def aggregate_by(self, col: int, by, filter_set: Optional[TableFilterSet] = None,
+                     residual: Optional[Residual] = None, txn: Optional[L.Txn] = None, ops: Optional[int] = None,
+                     path: Optional[str] = None, zonemap: bool = True) -> Dict[tuple, "Aggregate"]:
+        """SELECT by…, sum(col), min(col), max(col), count(col), count(*) WHERE <filter> GROUP BY by… →
+        {key tuple: Aggregate}, the keys as aggregate_groups gives them (None: the NULL group) and
+        each Aggregate as aggregate()'s. Groups without a qualifying row are left out. ops, path and
+        zonemap as aggregate()'s."""
+        type_ = self.types.get(col)
+        no_sum = type_ in (L.TYPE_FLOAT, L.TYPE_DOUBLE, L.TYPE_VARCHAR) or col in self.huge
+        if ops is None:
+            ops = L.AGG_ALL & ~(L.AGG_SUM if no_sum else 0)
+        if path not in (None, "slices", "column"):
+            raise ValueError(f"path {path!r}")
+        flags = int(ops) | {None: 0, "slices": L.AGG_FROM_SLICES, "column": L.AGG_FROM_COLUMN}[path]
+        flags |= 0 if zonemap else L.AGG_NO_ZONEMAP
+        groups = self.aggregate_groups(by)
+        cols, arr = self._group_cols(by)
+        plan = serialize(filter_set, residual)
+        nodes = to_ctypes(plan.nodes)
+        ng = len(groups)
+        out = self.ctx.alloc(max(ng, 1) * 48)
+        try:
+            L.check(self.lib.cubit_table_aggregate_grouped(self.handle, nodes, len(plan.nodes),
+                                                           C.byref(txn) if txn is not None else None, col, arr,
+                                                           len(cols), flags, C.c_void_p(out.addr), ng))
+            self.ctx.check()
+            res = out.download(np.int64, ng * 6).reshape(ng, 6) if ng else np.zeros((0, 6), dtype=np.int64)
+        finally:
+            out.free()
+        result = {}
+        for key, row in zip(groups, res):
+            lo, hi, mn, mx, cv, cr = (int(x) for x in row)
+            if cr == 0:
+                continue
+            total = (hi << 64) + (lo & (2 ** 64 - 1))
+            if type_ == L.TYPE_UINT64:
+                total &= 2 ** 128 - 1
+            some = cv > 0
+            result[key] = Aggregate(total, mn if (ops & L.AGG_MIN) and some else None,
+                                    mx if (ops & L.AGG_MAX) and some else None, cv, cr)
+        return result
+
+    def last_grouped(self):
+        """(whether the last aggregate_by() read the bit slices, its group count, the fused kernel's
+        launches — 0 on the column path)."""
+        fs, ng, nl = C.c_int(), C.c_uint32(), C.c_uint32()
+        L.check(self.lib.cubit_table_last_grouped(self.handle, C.byref(fs), C.byref(ng), C.byref(nl)))
+        return bool(fs.value), int(ng.value), int(nl.value)
 
     def last_sum_packed(self) -> bool:
         v = C.c_int()

@@ -794,6 +794,51 @@ int cubit_table_last_sum_packed(cubit_table *t, int *packed);
 int cubit_table_aggregate(cubit_table *t, const cubit_filter_node *nodes, uint32_t n_nodes, const cubit_txn *txn,
                           int col, uint32_t ops, int64_t *d_out);
 int cubit_table_last_aggregate(cubit_table *t, int *from_slices);
+
+/* SELECT g1 [, g2], sum(col), min(col), max(col), count(col), count(*) WHERE <filter> GROUP BY g1 [, g2]:
+ * cubit_table_aggregate per group, in one pass. Each of the one or two group columns carries a primary
+ * CUBIT_INDEX_EQUALITY index over every distinct value (built with n = 0, or kept so by appends and
+ * merges); anything else is CUBIT_ERR_UNSUPPORTED, naming the column. VARCHAR and HUGEINT / UHUGEINT
+ * group columns work: their equality indexes are over dictionary codes.
+ *   The slots of a group column, ascending: the index's keys; the values that one of the column's
+ * update records carries and that are no key (an MVCC update may move a row to a value the index has
+ * never seen); and one NULL slot, last, when the column is nullable or an update record sets it NULL
+ * (GROUP BY makes NULL a group of its own: the reference's hash and perfect-hash aggregates group NULL
+ * keys like any other, src/execution/operator/aggregate/physical_hash_aggregate.cpp,
+ * physical_perfecthash_aggregate.cpp). Group g = i1 * n2 + i2 over the slots of the two columns
+ * (n2 = 1 with one column); n1 * n2 above CUBIT_AGG_MAX_GROUPS is CUBIT_ERR_UNSUPPORTED.
+ *   cubit_table_aggregate_groups (host only) reports the numbering: *n_groups = n1 * n2, and for
+ * g < min(cap, *n_groups) keys[g * n_group_cols + c] = the slot's key of group column c in the form
+ * cubit_table_build_index_quantiles reports keys (FLOAT / DOUBLE bit patterns, UINT64 bits, a dictionary
+ * column's codes; 0 at a NULL slot) and key_is_null[g * n_group_cols + c] = 1 at a NULL slot. keys and
+ * key_is_null may be NULL. The numbering holds until a group column's index or update records change
+ * (build, append, merge, sync, set_updates).
+ *   cubit_table_aggregate_grouped writes, for group g at d_out + 6 * g (device, cap_groups * 6 int64),
+ * the six slots of cubit_table_aggregate: {sum_lo, sum_hi, min, max, count_valid, count_rows}, with its
+ * NULL handling, type rules, SUM refusal and ops (CUBIT_AGG_FROM_SLICES, _FROM_COLUMN and _NO_ZONEMAP
+ * included). A group with no qualifying row has six zeros (the caller omits it, as SQL does); so has
+ * every group of an empty partition or under a filter that folds to FALSE. cap_groups below the
+ * group count is CUBIT_ERR_CAPACITY. The result is ready on the context's stream with no host round
+ * trip.
+ *   From the slices (a usable bit-sliced index on col, and no update record of col or of a group
+ * column visible to txn): one fused kernel evaluates the filter program and aggregates a batch of
+ * groups per launch, each group's rows formed in registers as F AND E1 AND E2 of the group columns'
+ * equality bitvectors (the NULL slot: the complement of the column's validity), reading
+ * (b + K [+ 1] + the launch's group bitvectors) / 8 bytes per row of the evaluated zones; more groups
+ * than one launch takes run as further launches on the stream. A slot that exists only because of an
+ * update value has no bitvector and no rows on this path. From the column: scan into scratch, probe
+ * col and each group column with validity (visible MVCC updates applied), reduce per group. Without
+ * a force flag the path estimated to move fewer bytes runs; both give the same numbers.
+ * cubit_table_last_grouped tells which ran, the group count and the fused kernel's launches (0 on
+ * the column path); any of its pointers may be NULL. */
+#define CUBIT_AGG_MAX_GROUP_COLS 2
+#define CUBIT_AGG_MAX_GROUPS 256
+int cubit_table_aggregate_groups(cubit_table *t, const int *group_cols, uint32_t n_group_cols, int64_t *keys,
+                                 uint8_t *key_is_null, uint32_t cap, uint32_t *n_groups);
+int cubit_table_aggregate_grouped(cubit_table *t, const cubit_filter_node *nodes, uint32_t n_nodes,
+                                  const cubit_txn *txn, int col, const int *group_cols, uint32_t n_group_cols,
+                                  uint32_t ops, int64_t *d_out, uint32_t cap_groups);
+int cubit_table_last_grouped(cubit_table *t, int *from_slices, uint32_t *n_groups, uint32_t *n_launches);
 /* The slice path's kernel on a caller's slices, as cubit_bitslice_compare is the compare's: d_slices
  * as there (n_slices 0 ... 64 device pointers, each cubit_padded_words(n_rows) words, 16-byte
  * aligned), d_validity NULL = every row valid, read only below ceil(n_rows / 64) words; d_filter =
