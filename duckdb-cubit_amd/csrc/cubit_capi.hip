@@ -97,6 +97,7 @@ struct cubit_ctx {
     uint32_t lookback_spins = 0; // EvalArgs::spin_limit (cubit_ctx_set_lookback_spins; 0 = default)
     int decode_kernel = CUBIT_DECODE_AUTO;  // cubit_ctx_set_decode_kernel
     int last_decode = 0;                    // kernel of the last decode (CUBIT_DECODE_PAIRS / _RUNS)
+    bool last_from_list = false;            // the last decode read a row list, not the bitvector
     // zonemap skip: the live-tile list of a launch, staged in page-locked memory and copied to
     // the device on the stream; live_ev marks the copy done before the staging is rewritten
     uint32_t* live_host = nullptr;
@@ -210,6 +211,14 @@ int upload_live(cubit_ctx* ctx, const std::vector<uint32_t>& zones, uint32_t per
 
 enum class RunMode { kDecode, kCount };
 
+// What a decode of one bitvector alone does with the bitvector's row list (cubit_row_list.hpp):
+// write it beside the row ids (kRowListBuild), or read it in the bitvector's place (kRowListRead).
+struct RowListUse {
+    RowListStep step = kRowListNone;
+    uint16_t* off = nullptr;
+    uint32_t* lo_cnt = nullptr;
+};
+
 // Launch the evaluator over a compiled program (asynchronous on the context stream).
 //   kDecode: row ids as per-tile ascending runs + tile directory (ordered = lay them out in
 //            row order: the look-back decode writes them so, up to kLookbackMaxTiles tiles;
@@ -219,10 +228,11 @@ enum class RunMode { kDecode, kCount };
 int run_eval(cubit_ctx* ctx, const EvalProgram& prog, uint64_t n_rows, int64_t row_base, int64_t* rowids,
              uint64_t capacity, uint64_t* d_count, uint64_t* result_words, RunMode mode, bool timed = false,
              bool ordered = false, bool check_capacity = false, const std::vector<uint32_t>* live_zones = nullptr,
-             const uint64_t* tile_prefix = nullptr) {
+             const uint64_t* tile_prefix = nullptr, const RowListUse* row_list = nullptr) {
     // the directory describes only the decode launched here: a count, a failed launch or a
     // folded-away filter leaves no tiles behind for cubit_ctx_last_tiles to hand out
     ctx->last_tiles = 0;
+    ctx->last_from_list = false;
     // the claim ticket carries row sums in 48 bits (finish_ticket)
     if (n_rows >= (1ull << 47)) return fail(CUBIT_ERR_INVALID, "%llu rows exceed 2^47", (unsigned long long)n_rows);
     EvalArgs a{};
@@ -271,7 +281,25 @@ int run_eval(cubit_ctx* ctx, const EvalProgram& prog, uint64_t n_rows, int64_t r
     a.tile_prefix = prefixed ? tile_prefix : nullptr;
     a.rowids = order_pass ? ctx->tmp_ids : rowids;
     a.capacity = rowids ? capacity : 0;
-    if (live_zones) {
+    // a row list goes with the prefixed decode only: built as its side output, or read by a kernel of
+    // its own that visits every tile (an empty one costs a directory entry), so no live-tile list
+    const bool from_list = prefixed && prog.n_leaves == 1 && row_list && row_list->step == kRowListRead;
+    if (prefixed && prog.n_leaves == 1 && row_list && row_list->step == kRowListBuild) {
+        a.list_off = row_list->off;
+        a.list_lo = row_list->lo_cnt;
+    }
+    RowListArgs la{};
+    if (from_list) {
+        la.prefix = tile_prefix;
+        la.off = row_list->off;
+        la.lo_cnt = row_list->lo_cnt;
+        la.tiles = (uint32_t)tiles;
+        la.row_base = row_base;
+        la.rowids = a.rowids;
+        la.capacity = a.capacity;
+        la.count = d_count;
+    }
+    if (live_zones && !from_list) {
         static_assert(kZoneWords == 2048, "a zone is one decode tile");
         uint32_t n_live = 0;
         if (int rc = upload_live(ctx, *live_zones, 1, &a.live, &n_live)) return rc;
@@ -289,6 +317,10 @@ int run_eval(cubit_ctx* ctx, const EvalProgram& prog, uint64_t n_rows, int64_t r
     // measured slower: SF100 / 4 18.5 -> 21.0 µs, fewer workgroups than the last round's leave HBM
     // unsaturated; profiles/r06k_balanced_grid_not_kept.txt)
     const unsigned grid = (unsigned)(work <= max_grid ? work : work <= 2 * max_grid ? (work + 1) / 2 : max_grid);
+    auto launch = [&](hipEvent_t e0, hipEvent_t e1) {
+        return from_list ? launch_decode_row_list(la, ctx->dir, ctx->stream, e0, e1)
+                         : launch_eval_decode(a, ctx->dir, grid, ctx->stream, e0, e1, kernel, ctx->n_cus);
+    };
     if (tiles == 0) {  // no row: the count is 0 and no kernel runs
         if (start) ctx->n_timed--;
         HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
@@ -309,11 +341,12 @@ int run_eval(cubit_ctx* ctx, const EvalProgram& prog, uint64_t n_rows, int64_t r
         }
         HIP_CHECK(hipEventRecord(ctx->rep_ev[0], ctx->stream));
         for (uint32_t i = 1; i < ctx->repeat; ++i) {
-            HIP_CHECK(launch_eval_decode(a, ctx->dir, grid, ctx->stream, nullptr, nullptr, kernel, ctx->n_cus));
+            HIP_CHECK(launch(nullptr, nullptr));
             a.epoch = ++ctx->epoch;
         }
     }
-    HIP_CHECK(launch_eval_decode(a, ctx->dir, grid, ctx->stream, start, stop, kernel, ctx->n_cus));
+    HIP_CHECK(launch(start, stop));
+    ctx->last_from_list = from_list;
     if (ctx->repeat) {
         HIP_CHECK(hipEventRecord(ctx->rep_ev[1], ctx->stream));
         ctx->rep_launches = ctx->repeat;
@@ -440,6 +473,13 @@ int cubit_ctx_set_decode_kernel(cubit_ctx* ctx, int kernel) {
     if (kernel < CUBIT_DECODE_AUTO || kernel > CUBIT_DECODE_LOOKBACK) return fail(CUBIT_ERR_INVALID, "decode kernel %d", kernel);
     CUBIT_LOCK(ctx);
     ctx->decode_kernel = kernel;
+    return CUBIT_OK;
+}
+
+int cubit_ctx_last_decode_from_list(cubit_ctx* ctx, int* from_list) {
+    if (!ctx || !from_list) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(ctx);
+    *from_list = ctx->last_from_list ? 1 : 0;
     return CUBIT_OK;
 }
 
@@ -1006,6 +1046,7 @@ struct Updates {
 // that holds it and the leaf later plans put in the group's place.
 struct DerivedLeaf {
     std::unique_ptr<DevBuf> bv;
+    uint64_t block_bytes = 0;  // as allocated (the table's pool takes blocks of its own size only)
     Leaf leaf;
     // a chain: what it replaced, and the selectivity estimate made from it the first time a plan
     // asks (conj_selectivity; < 0 = not yet). The estimate reads the columns' zone statistics,
@@ -1083,6 +1124,11 @@ struct cubit_table {
         // this bitvector alone decodes (EvalArgs::tile_prefix); dropped with the zone map
         std::shared_ptr<DevBuf> prefix;
         std::vector<uint64_t> prefix_host;
+        // decodes of this bitvector alone so far, and its row list (cubit_row_list.hpp) once the
+        // second of them wrote it: off[prefix_host.back()] and lo_cnt[cnt.size()]. Dropped with the
+        // zone map, or alone when the budget needs its bytes (drop_row_lists); row_lists accounts it.
+        uint64_t solo_decodes = 0;
+        std::shared_ptr<DevBuf> list_off, list_lo;
     };
     std::unordered_map<const uint64_t*, ZoneMap> zones;
     std::unique_ptr<DevBuf> zone_dev;  // class bytes of the bitvectors being summarised
@@ -1116,27 +1162,74 @@ struct cubit_table {
     DerivedCache<DerivedLeaf> derived;
     std::unordered_map<const uint64_t*, DerivedLeaf*> derived_bvs;  // the entries by their bitvectors
     bool derived_budget_set = false;  // cubit_table_set_derived_budget (else: the default share)
+    // Row lists (cubit_row_list.hpp) of the bitvectors in `zones`, by bitvector: their bytes count
+    // against the derived budget beside the kept bitvectors, and they go first.
+    RowListBook<const uint64_t*> row_lists;
+    bool use_row_lists = true;  // cubit_table_use_row_lists
+    uint64_t list_scans = 0;    // decodes answered from a list
+    // The free blocks of dropped derived bitvectors (cap_words words each), handed to the next
+    // admission instead of a device allocation; bounded by the derived budget.
+    BlockPool<void*> bv_pool;
+    ~cubit_table() {
+        bv_pool.clear([](void* p) { (void)hipFree(p); });
+    }
 };
 
 namespace {
 
+// A derived bitvector leaves the cache: its block waits in the table's pool when that has room
+// (work queued on it is ahead of the next owner's in stream order); else the DevBuf frees it.
+void pool_derived_bv(cubit_table* t, DerivedLeaf& d) {
+    if (d.bv && d.bv->p && t->bv_pool.give(d.bv->p, d.block_bytes)) d.bv->p = nullptr;
+}
+
+// The pool follows the table's block size and the derived budget: free blocks of another size, or
+// beyond the budget, go back to the device (a budget of 0 keeps none).
+void size_bv_pool(cubit_table* t) {
+    t->bv_pool.reset(std::max<uint64_t>(t->cap_words, 1) * 8, t->derived.budget(), [](void* p) { (void)hipFree(p); });
+}
+
 // A table-owned bitvector is about to be written, grown or freed: every zone map goes (they
 // are recomputed on the next scan that needs them).
 void drop_zones(cubit_table* t) {
-    t->zones.clear();
+    t->zones.clear();  // the row lists with them
+    t->row_lists.clear();
     t->col_zones.clear();
     t->pred_zones.clear();
-    // the derived leaves combine bits that are about to change: they and their use counters go
-    t->derived.clear([](DerivedLeaf&) {});
+    // the derived leaves combine bits that are about to change: they and their use counters go,
+    // their blocks wait in the pool for the next admission
+    t->derived.clear([t](DerivedLeaf& d) { pool_derived_bv(t, d); });
     t->derived_bvs.clear();
 }
 
+// Every row list goes, the zone maps they hang on stay.
+void drop_row_lists(cubit_table* t) {
+    if (!t->row_lists.size()) return;
+    for (auto& kv : t->zones) {
+        kv.second.list_off.reset();
+        kv.second.list_lo.reset();
+    }
+    t->row_lists.clear();
+}
+
+// Row lists beyond what the budget leaves beside the kept bitvectors go, the oldest first.
+void shed_row_lists(cubit_table* t) {
+    t->row_lists.shed(t->derived.budget(), t->derived.bytes(), [t](const uint64_t* bv) {
+        auto it = t->zones.find(bv);
+        if (it == t->zones.end()) return;
+        it->second.list_off.reset();
+        it->second.list_lo.reset();
+    });
+}
+
 // A derived leaf leaves the cache: its zone map goes with it (the map is keyed by pointer, and
-// the address may be handed out again).
+// the address may be handed out again). The budget is short, so every row list went first.
 void forget_derived(cubit_table* t, DerivedLeaf& d) {
+    drop_row_lists(t);
     const uint64_t* bv = static_cast<const uint64_t*>(d.bv->p);
     t->zones.erase(bv);
     t->derived_bvs.erase(bv);
+    pool_derived_bv(t, d);
 }
 
 // The column's values or indexes changed: its patched leaves are stale.
@@ -1152,6 +1245,43 @@ void drop_patches(cubit_table* t, int col) {
 int alloc_table_bv(cubit_table* t, DevBuf& b, uint64_t written = 0) {
     const uint64_t words = std::max<uint64_t>(t->cap_words, 1);
     if (hipMalloc(&b.p, words * 8) != hipSuccess) return CUBIT_ERR_OOM;
+    written = std::min(written, words);
+    if (written < words &&
+        hipMemsetAsync(static_cast<uint64_t*>(b.p) + written, 0, (words - written) * 8, t->ctx->stream) != hipSuccess)
+        return CUBIT_ERR_HIP;
+    return CUBIT_OK;
+}
+
+// The same for a derived bitvector (a kept group or chain), from the table's pool when it holds a
+// block: hipMalloc of a 75 MB block measured 185-200 µs and blocks the device, inside the scan that
+// admits. A pooled block held another derived bitvector: words past its nwp are zero,
+// as alloc_table_bv left them, and the tail is cleared here all the same.
+int alloc_derived_bv(cubit_table* t, DevBuf& b, uint64_t written) {
+    size_bv_pool(t);
+    if (!t->bv_pool.take(&b.p)) {
+        const bool first = t->bv_pool.device_allocs() == 0;
+        if (int rc = alloc_table_bv(t, b, written)) return rc;
+        t->bv_pool.allocated();
+        // The table's first admission also takes the blocks of the next few (a repeated WHERE clause
+        // over three columns keeps two or three groups and then their chain), as far as the budget
+        // goes: those admissions, and every one after a write, then find a block waiting. One that
+        // cannot be had is simply not pooled.
+        const uint64_t bytes = t->bv_pool.block_bytes();
+        for (uint64_t i = 1; first && i < kDerivedSlabBlocks && (i + 1) * bytes <= t->derived.budget(); ++i) {
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                break;
+            }
+            t->bv_pool.allocated();
+            if (!t->bv_pool.give(p, bytes)) {
+                (void)hipFree(p);
+                break;
+            }
+        }
+        return CUBIT_OK;
+    }
+    const uint64_t words = std::max<uint64_t>(t->cap_words, 1);
     written = std::min(written, words);
     if (written < words &&
         hipMemsetAsync(static_cast<uint64_t*>(b.p) + written, 0, (words - written) * 8, t->ctx->stream) != hipSuccess)
@@ -2483,6 +2613,7 @@ namespace {
 // (patched leaves, scratch) is dropped by the caller.
 int grow_bitvectors(cubit_table* t, uint64_t words) {
     drop_zones(t);
+    t->bv_pool.clear([](void* p) { (void)hipFree(p); });  // blocks of the old size
     hipStream_t s = t->ctx->stream;
     auto regrow = [&](void*& p) -> int {
         void* np = nullptr;
@@ -4487,7 +4618,7 @@ bool derivable(const cubit_table* t, const ExprP& p, const cubit_txn* txn) {
 int keep_derived(cubit_table* t, const DerivedKey& key, uint64_t bytes, const ExprP& e, Leaf l, ExprP* out) {
     const bool is_chain = derived_is_chain(key);
     auto b = std::make_unique<DevBuf>();
-    if (alloc_table_bv(t, *b, padded_words(t->n_rows)) != CUBIT_OK) {  // the pass below writes those words
+    if (alloc_derived_bv(t, *b, padded_words(t->n_rows)) != CUBIT_OK) {  // the pass below writes those words
         (void)hipGetLastError();
         return CUBIT_OK;
     }
@@ -4499,9 +4630,11 @@ int keep_derived(cubit_table* t, const DerivedKey& key, uint64_t bytes, const Ex
     l.bv = words;
     DerivedLeaf d;
     d.bv = std::move(b);
+    d.block_bytes = std::max<uint64_t>(t->cap_words, 1) * 8;
     d.leaf = l;
     if (is_chain) d.replaced = e;
     t->derived_bvs[words] = t->derived.insert(key, bytes, std::move(d));
+    shed_row_lists(t);  // the bitvectors grew: lists keep only the room they leave
     *out = mk_leaf(l);
     return CUBIT_OK;
 }
@@ -4857,6 +4990,50 @@ const uint64_t* tile_prefix_of(cubit_table* t, const uint64_t* bv, int* rc) {
     return static_cast<const uint64_t*>(m.prefix->p);
 }
 
+// What this decode of `bv` alone (its prefix is built) does with the bitvector's row list
+// (row_list_step): nothing the first time; the second time, when the byte rule holds and the budget
+// has room nobody uses, the list's buffers are made here and the decode fills them; later decodes
+// read them. A list that cannot be allocated is not built: the decode reads the bitvector.
+int plan_row_list(cubit_table* t, const uint64_t* bv, RowListUse* use) {
+    auto it = t->zones.find(bv);
+    if (it == t->zones.end() || it->second.prefix_host.empty()) return CUBIT_OK;
+    cubit_table::ZoneMap& m = it->second;
+    const uint64_t tiles = m.cnt.size(), q = m.prefix_host.back(), bytes = row_list_bytes(q, tiles);
+    const bool on = t->use_row_lists;
+    const RowListStep step =
+        row_list_step(m.solo_decodes++, on && m.list_off, on && row_list_wanted(q, tiles, t->nwp * 8), bytes,
+                      t->row_lists.room(t->derived.budget(), t->derived.bytes()));
+    if (step == kRowListBuild) {
+        auto off = std::make_shared<DevBuf>(), lo = std::make_shared<DevBuf>();
+        if (hipMalloc(&off->p, std::max<uint64_t>(2 * q, 16)) != hipSuccess ||
+            hipMalloc(&lo->p, std::max<uint64_t>(4 * tiles, 16)) != hipSuccess) {
+            (void)hipGetLastError();
+            return CUBIT_OK;
+        }
+        // a tile the zone maps let the decode skip holds no row
+        HIP_CHECK(hipMemsetAsync(lo->p, 0, std::max<uint64_t>(4 * tiles, 16), t->ctx->stream));
+        m.list_off = std::move(off);
+        m.list_lo = std::move(lo);
+        t->row_lists.add(bv, bytes);
+    }
+    if (step != kRowListNone) {
+        use->step = step;
+        use->off = static_cast<uint16_t*>(m.list_off->p);
+        use->lo_cnt = static_cast<uint32_t*>(m.list_lo->p);
+    }
+    return CUBIT_OK;
+}
+
+// The list a failed building scan left half written goes.
+void drop_row_list(cubit_table* t, const uint64_t* bv) {
+    auto it = t->zones.find(bv);
+    if (it != t->zones.end()) {
+        it->second.list_off.reset();
+        it->second.list_lo.reset();
+    }
+    t->row_lists.drop(bv);
+}
+
 // The values `col` can take among the rows the filter keeps, when its constant filters in the
 // top-level AND pin it to a short list that the column's exact range index can decode:
 // v0 < v1 < … with leaves L(v_j). Returns false when it cannot (the kernel then gathers b).
@@ -4913,6 +5090,7 @@ extern "C" int cubit_table_scan(cubit_table* t, const cubit_filter_node* nodes, 
     if (n_nodes && !nodes) return fail(CUBIT_ERR_INVALID, "nodes is null");
     if (int rc = set_device(t->ctx)) return rc;
     t->ctx->last_tiles = 0;  // until this scan's decode is launched (a planning error leaves none)
+    t->ctx->last_from_list = false;
     if (t->n_rows == 0) {  // empty partition
         t->last_leaves = t->last_passes = 0;
         t->last_live = t->last_zones = 0;
@@ -4940,11 +5118,18 @@ extern "C" int cubit_table_scan(cubit_table* t, const cubit_filter_node* nodes, 
         prefix = tile_prefix_of(t, t->single_leaf, &rc);
         if (rc) return rc;
     }
+    // the decode that takes the prefix (no PAIRS or RUNS kernel forced) may write or read a row list
+    RowListUse row_list;
+    const int forced = t->ctx->decode_kernel;
+    if (prefix && (forced == CUBIT_DECODE_AUTO || forced == CUBIT_DECODE_LOOKBACK))
+        if (int rc = plan_row_list(t, t->single_leaf, &row_list)) return rc;
     const uint64_t h2 = host_timing() ? now_ns() : 0;
     const int rc = run_eval(t->ctx, em.prog, t->n_rows, t->row_base, count_only ? nullptr : d_rowids, capacity, d_count,
                             nullptr, count_only ? RunMode::kCount : RunMode::kDecode, true,
                             (flags & CUBIT_SCAN_ORDERED) != 0, (flags & CUBIT_SCAN_CHECK_CAPACITY) != 0,
-                            live.empty() ? nullptr : &live, prefix);
+                            live.empty() ? nullptr : &live, prefix, &row_list);
+    if (row_list.step == kRowListBuild && !t->ctx->last_tiles) drop_row_list(t, t->single_leaf);  // no launch
+    if (t->ctx->last_from_list) t->list_scans++;
     if (host_timing()) {
         const uint64_t h3 = now_ns();
         t->host_ns[0] += h1 - h0;
@@ -5492,6 +5677,32 @@ extern "C" int cubit_table_set_derived_budget(cubit_table* t, uint64_t bytes) {
     if (int rc = set_device(t->ctx)) return rc;
     t->derived_budget_set = true;
     t->derived.set_budget(bytes, [t](DerivedLeaf& d) { forget_derived(t, d); });
+    size_bv_pool(t);
+    shed_row_lists(t);
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_derived_pool_stats(cubit_table* t, uint32_t* free_blocks, uint64_t* device_allocs) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    if (free_blocks) *free_blocks = (uint32_t)t->bv_pool.free_blocks();
+    if (device_allocs) *device_allocs = t->bv_pool.device_allocs();
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_use_row_lists(cubit_table* t, int on) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    t->use_row_lists = on != 0;
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_row_list_stats(cubit_table* t, uint32_t* lists, uint64_t* bytes, uint64_t* scans_from_lists) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    if (lists) *lists = (uint32_t)t->row_lists.size();
+    if (bytes) *bytes = t->row_lists.bytes();
+    if (scans_from_lists) *scans_from_lists = t->list_scans;
     return CUBIT_OK;
 }
 

@@ -125,7 +125,10 @@ inline bool derived_chain_admit(uint64_t uses_so_far, uint64_t k, uint64_t B, ui
 // (DESIGN.md §3): the scan that admitted the l_discount interval took 413 µs longer than the plain
 // scans after it, 38 µs of them the bits-only pass's own 225 MB; the other 376 µs at the 5.97 TB/s
 // of that scan's byte mix. SF100 Q6 (k = 3, B = 75 MB) is bought at its 18th request; a 300,001-row
-// table (B = 131 KB as allocated) would need some 8,500.
+// table (B = 131 KB as allocated) would need some 8,500. That scan allocated its block; an admitting
+// scan that takes a block of the table's pool (cubit_row_list.hpp) measures 0.196 GB
+// (profiles/r15_admission_cost.txt). The constant stays at the allocating scan's cost, which a table's
+// first admission still pays: tests/derived_chain_core.cpp pins the admission points it gives.
 constexpr uint64_t kDerivedChainCost = 2'240'000'000ull;
 
 // The cache of materialised combinations (payload P: whatever owns the bitvector) and the use

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "cubit_program.hpp"
+#include "cubit_row_list.hpp"
 #include "cubit_segments.hpp"
 
 namespace cubit {
@@ -107,6 +108,23 @@ struct EvalArgs {
     // launch (a program of one index bitvector: its per-zone counts, a zone being one decode
     // tile), or null. With it no workgroup publishes or waits, at any tile count.
     const uint64_t* tile_prefix;
+    // the prefixed decode's side output (both or neither; cubit_row_list.hpp): the low 16 bits of
+    // every qualifying row's tile-local offset at list_off[tile_prefix[tile] + i], whatever the
+    // capacity, and the tile's rows below 65,536 at list_lo[tile]
+    uint16_t* list_off;
+    uint32_t* list_lo;
+};
+// decode_row_list_kernel: a bitvector's row list (cubit_row_list.hpp) into what the prefixed decode
+// of the bitvector writes
+struct RowListArgs {
+    const uint64_t* prefix;  // tiles + 1 entries
+    const uint16_t* off;
+    const uint32_t* lo_cnt;
+    uint32_t tiles;
+    int64_t row_base;
+    int64_t* rowids;
+    uint64_t capacity;
+    uint64_t* count;
 };
 // eval_decode_lookback: one workgroup per tile, at most this many tiles per launch (6.0e8 rows).
 // Every workgroup reads the counts of all earlier tiles, so the flag reads grow with the square
@@ -140,6 +158,9 @@ int decode_kernel_for(uint32_t n_leaves, uint32_t num_tiles, unsigned grid, int 
 uint32_t lookback_max_tiles(uint32_t n_leaves, int n_cus);
 hipError_t launch_eval_decode(const EvalArgs& a, uint64_t* dir, unsigned grid, hipStream_t stream,
                               hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int kernel = 0, int n_cus = 256);
+// row ids, tile directory and count from a row list: one workgroup per tile, no bitvector read
+hipError_t launch_decode_row_list(const RowListArgs& a, uint64_t* dir, hipStream_t stream, hipEvent_t ev0 = nullptr,
+                                  hipEvent_t ev1 = nullptr);
 // zone classes of a bitvector (class byte per zone, see kZoneWords) for zones [z0, z0 + nz),
 // and (cnt non-null) each zone's set rows
 hipError_t launch_zone_classes(const uint64_t* bv, uint64_t n_rows, uint32_t z0, uint32_t nz, uint8_t* out,

@@ -325,6 +325,13 @@ __device__ __forceinline__ void emit_ids(int64_t* rowids, uint64_t capacity, con
     }
 }
 
+// The prefixed decode's side output (cubit_row_list.hpp): list[base + i] = the low 16 bits of st[i] for
+// i < n. Written once per bitvector, by the scan that builds its row list.
+template <int THREADS>
+__device__ __forceinline__ void emit_list(uint16_t* list, const uint32_t* st, uint32_t n, uint64_t base, int t) {
+    for (uint32_t i = t; i < n; i += THREADS) list[base + i] = row_list_encode(st[i]);
+}
+
 // The i-th tile of a launch: entry i of the planner's live-tile list (zonemap skip) or i itself.
 // i is uniform, so the list entry is a scalar load; callers fetch it one tile ahead.
 __device__ __forceinline__ uint32_t tile_at(const EvalArgs& a, uint32_t i) { return a.live ? a.live[i] : i; }
@@ -1249,6 +1256,9 @@ __global__ __launch_bounds__(THREADS, WPC * THREADS / 256) void eval_decode_look
     // no workgroup publishes or waits
     const bool prefixed = PRE || a.tile_prefix != nullptr;
     const uint64_t known_base = prefixed ? a.tile_prefix[tile] : 0;
+    // the row list's side output never passes the tile's own slice of the list
+    const bool listed = PRE && a.list_off != nullptr;
+    const uint64_t known_next = listed ? a.tile_prefix[tile + 1] : 0;
     if (t == 0) s_expired = 0;
     u64x2 v[K][PAIRS];
     load_tile<K, PAIRS, THREADS>(a, tile_word0, t, v);
@@ -1366,10 +1376,13 @@ __global__ __launch_bounds__(THREADS, WPC * THREADS / 256) void eval_decode_look
             dir[2 * tile + 1] = tile_count;
         }
         if (b == gridDim.x - 1) *a.count = base + tile_count;
+        if (listed) a.list_lo[tile] = block_tot[0];
     }
     if (!write_ids || !tile_count || (DBG & 2)) return;
+    const uint32_t list_n = listed && known_next > base ? (uint32_t)min((uint64_t)tile_count, known_next - base) : 0;
     if (staged) {
         emit_ids<THREADS, SAUX>(a.rowids, a.capacity, s_stage, tile_count, base, row0, t);
+        if (listed) emit_list<THREADS>(a.list_off, s_stage, list_n, base, t);
         return;
     }
     // dense tile: rounds of STAGE ids through the stage, its result words back from s_words (no
@@ -1403,6 +1416,55 @@ __global__ __launch_bounds__(THREADS, WPC * THREADS / 256) void eval_decode_look
         }
         __syncthreads();
         emit_ids<THREADS, SAUX>(a.rowids, a.capacity, s_stage, r1 - r0, base + r0, row0, t);
+        if (listed && r0 < list_n) emit_list<THREADS>(a.list_off, s_stage, min(r1, list_n) - r0, base + r0, t);
+    }
+}
+
+// Row ids, tile directory and count of a bitvector from its row list (cubit_row_list.hpp), exactly as
+// the prefixed decode above writes them: one workgroup per tile, ids row_base + tile * 131,072 + offset
+// at rowids[prefix[tile] + i], those at or past `capacity` dropped, dir = {count ? prefix[tile] : 0,
+// count} for every tile. Reads 2 bytes per id where the decode reads the bitvector; the stores follow
+// emit_ids (16-byte sc1 buffer stores from the first 16-byte boundary on).
+template <int THREADS, int SAUX>
+__global__ __launch_bounds__(THREADS) void decode_row_list_kernel(RowListArgs a, uint64_t* __restrict__ dir) {
+    typedef int64_t i64x2 __attribute__((ext_vector_type(2)));
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const int t = threadIdx.x;
+    const uint32_t tile = blockIdx.x;
+    const uint64_t base = a.prefix[tile];
+    const uint64_t next = a.prefix[tile + 1];
+    const uint32_t n = next > base ? (uint32_t)min(next - base, (uint64_t)kRowListTileRows) : 0;
+    const uint32_t lo = a.lo_cnt[tile];
+    if (t == 0) {
+        if (dir) {
+            dir[2 * tile] = n ? base : 0;
+            dir[2 * tile + 1] = n;
+        }
+        if (tile == gridDim.x - 1) *a.count = base + n;
+    }
+    const uint64_t room = a.capacity > base ? a.capacity - base : 0;
+    const uint32_t lim = (uint32_t)(room < (uint64_t)n ? room : (uint64_t)n);
+    if (!a.rowids || lim == 0) return;
+    const int64_t row0 = a.row_base + (int64_t)((uint64_t)tile * kRowListTileRows);
+    int64_t* out = a.rowids + base;
+    const uint16_t* src = a.off + base;
+    const uint32_t head = min(lim, (uint32_t)(((16 - (reinterpret_cast<uintptr_t>(out) & 15)) & 15) >> 3));
+    const uint64_t ob = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)out >> 32)) << 32) |
+                        (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)out);
+    const uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane(lim) * 8u;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)ob, (short)0, (int)nb, 0x00020000);
+    auto id = [&](uint32_t i) { return row0 + (int64_t)row_list_decode(src[i], i, lo); };
+    if (t < (int)head) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, id((uint32_t)t)), rs, t * 8, 0, SAUX);
+    for (uint32_t i = head + 2 * t; i < lim; i += 2 * THREADS) {
+        if (i + 1 < lim) {
+            i64x2 val;
+            val.x = id(i);
+            val.y = id(i + 1);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, val), rs, (int)(i * 8u), 0, SAUX);
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, id(i)), rs, (int)(i * 8u), 0, SAUX);
+        }
     }
 }
 
@@ -4349,6 +4411,7 @@ constexpr int kLookbackStage = 8192;
 // entries measured the same (30.8), one of 2,048 (most tiles in rounds) 37.8
 // (profiles/r13_prefixed_decode.txt)
 constexpr int kPrefixedWpc = 4;
+constexpr int kRowListThreads = 512;  // decode_row_list_kernel: one workgroup per tile
 uint32_t lookback_max_tiles(uint32_t n_leaves, int n_cus) {
     return std::min<uint32_t>(kLookbackMaxTiles, (uint32_t)lookback_wpc(n_leaves) * (uint32_t)n_cus);
 }
@@ -4403,6 +4466,13 @@ hipError_t launch_eval_decode(const EvalArgs& a, uint64_t* dir, unsigned grid, h
         launch_decode_kf<k.value, form.value>(a, dir, grid, s, e0, e1, kernel, n_cus);
     });
     return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_decode_row_list(const RowListArgs& a, uint64_t* dir, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    if (a.tiles == 0 || !a.prefix || !a.off || !a.lo_cnt || !a.count) return hipErrorInvalidValue;
+    hipExtLaunchKernelGGL((decode_row_list_kernel<kRowListThreads, 16>), dim3(a.tiles), dim3(kRowListThreads), 0, s, e0,
+                          e1, 0, a, dir);
+    return hipGetLastError();
 }
 
 hipError_t launch_eval_count(const EvalArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {

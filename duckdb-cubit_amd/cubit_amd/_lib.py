@@ -182,6 +182,9 @@ GPU_SIGNATURES = {
     "cubit_table_derived_stats": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U64), C.POINTER(_U64)]),
     "cubit_table_set_derived_chain_cost": (C.c_int, [_P, _U64]),
     "cubit_table_derived_chain_stats": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U64)]),
+    "cubit_table_derived_pool_stats": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U64)]),
+    "cubit_table_use_row_lists": (C.c_int, [_P, C.c_int]),
+    "cubit_table_row_list_stats": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U64), C.POINTER(_U64)]),
     "cubit_table_estimate_rows": (C.c_int, [_P, C.POINTER(FilterNode), _U32, C.POINTER(_U64)]),
     "cubit_table_last_zones": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U32)]),
     "cubit_table_use_packed_filter": (C.c_int, [_P, C.c_int]),
@@ -211,6 +214,7 @@ GPU_SIGNATURES = {
     "cubit_host_alloc": (C.c_int, [_P, _U64, C.POINTER(_P)]),
     "cubit_host_free": (C.c_int, [_P, _P]),
     "cubit_ctx_last_decode_kernel": (C.c_int, [_P, _P]),
+    "cubit_ctx_last_decode_from_list": (C.c_int, [_P, _P]),
     "cubit_table_merge_updates": (C.c_int, [_P, C.c_int, _U64, _P]),
     "cubit_table_sync_column": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _U64, C.POINTER(_U64), C.POINTER(C.c_int)]),
     "cubit_table_save_index": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p]),

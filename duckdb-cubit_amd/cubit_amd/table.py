@@ -44,6 +44,13 @@ class Context:
         L.check(self.lib.cubit_ctx_last_decode_kernel(self.handle, C.byref(k)))
         return int(k.value)
 
+    def last_decode_from_list(self) -> bool:
+        """Whether the last decode read a row list in the bitvector's place (it reports
+        L.DECODE_PREFIXED as its kernel all the same)."""
+        f = C.c_int()
+        L.check(self.lib.cubit_ctx_last_decode_from_list(self.handle, C.byref(f)))
+        return bool(f.value)
+
     def enable_timing(self, on: bool = True) -> None:
         L.check(self.lib.cubit_ctx_enable_timing(self.handle, 1 if on else 0))
 
@@ -841,6 +848,25 @@ class CubitTable:
         h = C.c_uint64()
         L.check(self.lib.cubit_table_derived_chain_stats(self.handle, C.byref(n), C.byref(h)))
         return int(n.value), int(h.value)
+
+    def derived_pool_stats(self):
+        """(free blocks waiting for the next admission, device allocations of such blocks so far)."""
+        n = C.c_uint32()
+        a = C.c_uint64()
+        L.check(self.lib.cubit_table_derived_pool_stats(self.handle, C.byref(n), C.byref(a)))
+        return int(n.value), int(a.value)
+
+    def use_row_lists(self, on: bool = True) -> None:
+        """Build and read row lists (sparse bitvectors that scans decode alone, kept as 16-bit offsets)."""
+        L.check(self.lib.cubit_table_use_row_lists(self.handle, 1 if on else 0))
+
+    def row_list_stats(self):
+        """(row lists held, their bytes, decodes answered from a list so far)."""
+        n = C.c_uint32()
+        b = C.c_uint64()
+        s = C.c_uint64()
+        L.check(self.lib.cubit_table_row_list_stats(self.handle, C.byref(n), C.byref(b), C.byref(s)))
+        return int(n.value), int(b.value), int(s.value)
 
     def close(self) -> None:
         # a partition never outlives its context (Context.close destroys it first)

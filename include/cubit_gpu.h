@@ -254,6 +254,10 @@ int cubit_ctx_set_lookback_spins(cubit_ctx *ctx, uint32_t spins);
 /* The kernel the context's last decode launched (CUBIT_DECODE_PAIRS, _RUNS, _LOOKBACK or _PREFIXED; 0 when
  * the partition had no row and nothing was launched). */
 int cubit_ctx_last_decode_kernel(cubit_ctx *ctx, int *kernel);
+/* Whether the last decode read the bitvector's row list (cubit_table_row_list_stats) in the
+ * bitvector's place. Such a decode reports CUBIT_DECODE_PREFIXED above: its offsets are known up
+ * front all the same, and it writes what the prefixed kernel writes. */
+int cubit_ctx_last_decode_from_list(cubit_ctx *ctx, int *from_list);
 /* Filter-kernel durations measured with HIP events recorded around each launch on the
  * context stream (ms); requires cubit_ctx_enable_timing(ctx, 1). */
 int cubit_ctx_enable_timing(cubit_ctx *ctx, int on);
@@ -713,6 +717,26 @@ int cubit_table_set_derived_chain_cost(cubit_table *t, uint64_t fixed_bytes);
 /* Kept chains (counted in cubit_table_derived_stats' leaves and bytes too) and the chains that plans
  * replaced by one leaf so far (counted in its hits too). Any pointer may be NULL. */
 int cubit_table_derived_chain_stats(cubit_table *t, uint32_t *chains, uint64_t *hits);
+/* The blocks of kept combinations that were dropped (every write to the table drops them all; the
+ * budget evicts) wait in a table-owned free list, bounded by the derived budget, and the next
+ * admission takes one instead of allocating inside its scan. The table's first admission allocates
+ * up to four blocks, as far as the budget goes. free_blocks: blocks waiting; device_allocs: device
+ * allocations of such blocks since the table was created. The list is emptied when the budget is
+ * set to 0, when the table's bitvectors grow, and with the table. */
+int cubit_table_derived_pool_stats(cubit_table *t, uint32_t *free_blocks, uint64_t *device_allocs);
+/* Row lists. A table-owned bitvector that a scan decodes alone (one index leaf, a kept group or
+ * chain) and that is sparse enough is also kept as a list of its set rows: 2 bytes per row and 4 per
+ * 131,072-row tile, wanted only when that is at most half the bitvector's bytes. The first such
+ * decode of a bitvector pays nothing, the second writes the list beside its row ids, later ones read
+ * the list and not the bitvector; row ids, tile directory and count are the same. A list's bytes
+ * count against the derived budget: it is built only into room nothing else uses (a budget of 0:
+ * never), goes before any kept bitvector does, and with its bitvector's zone map on every write to
+ * the table. Forced PAIRS / RUNS decodes never read one. on = 0 stops building and reading (lists
+ * held stay until dropped); default on. */
+int cubit_table_use_row_lists(cubit_table *t, int on);
+/* Lists held, their bytes (not part of cubit_table_derived_stats' bytes), and the decodes answered
+ * from a list so far. Any pointer may be NULL. */
+int cubit_table_row_list_stats(cubit_table *t, uint32_t *lists, uint64_t *bytes, uint64_t *scans_from_lists);
 /* Column statistics — DataTable::GetStatistics behind seq_scan's `statistics` callback
  * (TableScanStatistics, src/function/table/table_scan.cpp:108-117): min / max of the valid
  * values (widened by the column's update records, as UpdateSegment merges updates into the
