@@ -91,6 +91,7 @@ struct cubit_ctx {
     int64_t* gkeys_host = nullptr;
     hipEvent_t gkeys_ev = nullptr;
     bool gkeys_pending = false;
+    int64_t* sel = nullptr;      // workspace of the select kernels (kSelectWorkspace int64; ensure_select)
     uint64_t* ticket = nullptr;  // claim ticket of the evaluate kernels (EvalArgs::ticket)
     uint64_t* flags = nullptr;   // look-back flag words of eval_decode_lookback (EvalArgs::flags)
     uint64_t epoch = 0;          // the last look-back launch's epoch (EvalArgs::epoch)
@@ -152,6 +153,16 @@ int ensure_tmp(cubit_ctx* ctx, uint64_t cap) {
 
 int set_device(cubit_ctx* ctx) {
     HIP_CHECK(hipSetDevice(ctx->device));
+    return CUBIT_OK;
+}
+
+// the select kernels' workspace, allocated by the first select on the context
+int ensure_select(cubit_ctx* ctx) {
+    if (ctx->sel) return CUBIT_OK;
+    if (hipMalloc(&ctx->sel, kSelectWorkspace * sizeof(int64_t)) != hipSuccess) {
+        ctx->sel = nullptr;
+        return fail(CUBIT_ERR_OOM, "select workspace allocation failed");
+    }
     return CUBIT_OK;
 }
 
@@ -427,6 +438,7 @@ int cubit_ctx_destroy(cubit_ctx* ctx) {
     if (ctx->agg) (void)hipFree(ctx->agg);
     if (ctx->gkeys_pending) (void)hipEventSynchronize(ctx->gkeys_ev);
     if (ctx->gagg) (void)hipFree(ctx->gagg);
+    if (ctx->sel) (void)hipFree(ctx->sel);
     if (ctx->gkeys_dev) (void)hipFree(ctx->gkeys_dev);
     if (ctx->gkeys_host) (void)hipHostFree(ctx->gkeys_host);
     if (ctx->gkeys_ev) (void)hipEventDestroy(ctx->gkeys_ev);
@@ -830,6 +842,51 @@ int cubit_bitslice_aggregate(cubit_ctx* ctx, const uint64_t* const* d_slices, ui
     return CUBIT_OK;
 }
 
+int cubit_bitslice_select(cubit_ctx* ctx, const uint64_t* const* d_slices, uint32_t n_slices, const uint64_t* d_validity,
+                          const uint64_t* d_filter, uint64_t n_rows, int type, int64_t base, int mode, uint64_t k, double q,
+                          int64_t* d_out) {
+    if (!ctx || !d_out || (n_slices && !d_slices)) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(ctx);
+    if (n_slices > kMaxSlices) return fail(CUBIT_ERR_INVALID, "%u slices (0 … 64)", n_slices);
+    if (mode != CUBIT_SELECT_RANK && mode != CUBIT_SELECT_RANK_DESC && mode != CUBIT_SELECT_QUANTILE)
+        return fail(CUBIT_ERR_INVALID, "mode %d", mode);
+    if (mode == CUBIT_SELECT_QUANTILE && !(q >= 0.0 && q <= 1.0)) return fail(CUBIT_ERR_INVALID, "quantile %g outside [0, 1]", q);
+    if (type != CUBIT_TYPE_INT32 && type != CUBIT_TYPE_INT64 && type != CUBIT_TYPE_VARCHAR && !type_is_keyed(type))
+        return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
+    if (n_rows >= (1ull << 47)) return fail(CUBIT_ERR_INVALID, "%llu rows exceed 2^47", (unsigned long long)n_rows);
+    auto aligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    if (!aligned(d_filter) || !aligned(d_validity)) return fail(CUBIT_ERR_INVALID, "bitvectors must be 16-byte aligned");
+    SliceSelectArgs g{};
+    for (uint32_t s = 0; s < n_slices; ++s) {
+        if (!d_slices[s] || !aligned(d_slices[s])) return fail(CUBIT_ERR_INVALID, "slice %u is null or unaligned", s);
+        g.slices.s[s] = const_cast<uint64_t*>(d_slices[s]);
+    }
+    if (int rc = set_device(ctx)) return rc;
+    if (n_rows == 0) {  // no rows: zero counts, nothing to launch
+        HIP_CHECK(hipMemsetAsync(d_out, 0, 6 * sizeof(int64_t), ctx->stream));
+        return CUBIT_OK;
+    }
+    if (int rc = ensure_select(ctx)) return rc;
+    if (int rc = ensure_tmp(ctx, padded_words(n_rows))) return rc;  // the candidate bitvector
+    g.n_slices = n_slices;
+    g.validity = d_validity;
+    g.cand = reinterpret_cast<uint64_t*>(ctx->tmp_ids);
+    g.workspace = ctx->sel;
+    EvalArgs a{};
+    if (d_filter) {  // a one-leaf program; NULL: the zero-leaf form, every row below n_rows
+        a.prog.leaf[0] = d_filter;
+        a.prog.n_leaves = 1;
+    }
+    a.n_rows = n_rows;
+    a.n_words = (n_rows + 63) / 64;
+    a.ticket = ctx->ticket;
+    a.num_tiles = (uint32_t)((a.n_words + kAggTileWords - 1) / kAggTileWords);  // the tiles that hold rows
+    hipEvent_t e0, e1;
+    if (int rc = timing_events(ctx, e0, e1)) return rc;
+    HIP_CHECK(launch_slice_select(a, g, mode, k, q, type, base, ctx->n_cus, d_out, ctx->stream, nullptr, e0, e1));
+    return CUBIT_OK;
+}
+
 }  // extern "C"
 
 extern "C" int cubit_bitvector_eval(cubit_ctx* ctx, const uint64_t* const* d_leaves, uint32_t n_leaves,
@@ -1152,6 +1209,8 @@ struct cubit_table {
     std::vector<int32_t> last_narrow_cols;  // columns of the last plan's K0 leaves, in build order
     bool last_sum_packed = false;  // the last sum_product read a from its BITPACKING segments
     bool last_agg_slices = false;  // the last cubit_table_aggregate read the column's slices
+    bool last_sel_slices = false;  // the last cubit_table_select read the column's slices
+    uint32_t last_sel_passes = 0;  // its passes over the slices or the probed values
     // the last cubit_table_aggregate_grouped: its path, group count and fused-kernel launches
     bool last_grouped_slices = false;
     uint32_t last_grouped_groups = 0, last_grouped_launches = 0;
@@ -5381,6 +5440,194 @@ extern "C" int cubit_table_last_aggregate(cubit_table* t, int* from_slices) {
     if (!t || !from_slices) return fail(CUBIT_ERR_INVALID, "null argument");
     CUBIT_LOCK(t->ctx);
     *from_slices = t->last_agg_slices ? 1 : 0;
+    return CUBIT_OK;
+}
+
+// SELECT the k-th value / quantile_disc of col WHERE <filter>: cubit_table_aggregate's two paths with
+// a radix select in the reduction's place. select_from_slices (cubit_program.hpp) chooses.
+extern "C" int cubit_table_select(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_nodes, const cubit_txn* txn,
+                                  int col, int mode, uint64_t k, double q, uint32_t flags, int64_t* d_out) {
+    if (!t || !d_out) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    if (n_nodes && !nodes) return fail(CUBIT_ERR_INVALID, "nodes is null");
+    if (mode != CUBIT_SELECT_RANK && mode != CUBIT_SELECT_RANK_DESC && mode != CUBIT_SELECT_QUANTILE)
+        return fail(CUBIT_ERR_INVALID, "mode %d", mode);
+    if (mode == CUBIT_SELECT_QUANTILE && !(q >= 0.0 && q <= 1.0)) return fail(CUBIT_ERR_INVALID, "quantile %g outside [0, 1]", q);
+    if (flags & ~(CUBIT_SELECT_FROM_SLICES | CUBIT_SELECT_FROM_COLUMN | CUBIT_SELECT_NO_ZONEMAP))
+        return fail(CUBIT_ERR_INVALID, "flags %u", flags);
+    const bool force_slices = (flags & CUBIT_SELECT_FROM_SLICES) != 0, force_column = (flags & CUBIT_SELECT_FROM_COLUMN) != 0;
+    if (force_slices && force_column) return fail(CUBIT_ERR_INVALID, "both paths forced");
+    auto cit = t->cols.find(col);
+    if (cit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column %d not registered", col);
+    const Column& c = cit->second;
+    if (int rc = set_device(t->ctx)) return rc;
+    cubit_ctx* ctx = t->ctx;
+    ctx->last_tiles = 0;  // no row ids reach the caller, so no tile directory
+    auto sit = t->sliced.find(col);
+    auto uit = t->upd.find(col);
+    const bool visible_updates = txn && uit != t->upd.end() && uit->second.any_visible(txn);
+    const bool usable = sit != t->sliced.end() && !sit->second.empty && t->use_sliced && !visible_updates;
+    if (force_slices && !usable)
+        return fail(CUBIT_ERR_INVALID, "column %d has no usable bit-sliced index%s", col,
+                    visible_updates ? " (an update record is visible to the transaction)" : "");
+    t->last_sel_slices = false;
+    t->last_sel_passes = 0;
+    if (t->n_rows == 0) {  // empty partition: zero counts, found = 0
+        t->last_leaves = t->last_passes = 0;
+        t->last_live = t->last_zones = 0;
+        t->last_sliced = 0;
+        HIP_CHECK(hipMemsetAsync(d_out, 0, 6 * sizeof(int64_t), ctx->stream));
+        return CUBIT_OK;
+    }
+    uint64_t est_rows = t->n_rows;
+    if (usable && !force_slices && !force_column)
+        if (int rc = cubit_table_estimate_rows(t, nodes, n_nodes, &est_rows)) return rc;
+    Emitter em;
+    bool empty = false;
+    std::vector<uint32_t> live;
+    t->last_zones = real_zones(t);
+    t->last_live = 0;
+    if (int rc = plan_program(t, nodes, n_nodes, txn, em, &empty, (flags & CUBIT_SELECT_NO_ZONEMAP) ? nullptr : &live))
+        return rc;
+    if (empty) {  // the filter folded to FALSE (or the zonemaps rule out every zone)
+        HIP_CHECK(hipMemsetAsync(d_out, 0, 6 * sizeof(int64_t), ctx->stream));
+        return CUBIT_OK;
+    }
+    if (int rc = ensure_select(ctx)) return rc;
+    t->last_live = live.empty() ? t->last_zones : (uint32_t)live.size();
+    const uint64_t live_rows = std::min<uint64_t>(t->n_rows, (uint64_t)t->last_live * kZoneRows);
+    const uint32_t bits = usable ? (uint32_t)sit->second.bvs.size() : 0;
+    if (select_from_slices(force_slices, force_column, usable, bits, em.prog.n_leaves, c.validity != nullptr, live_rows,
+                           t->n_rows, est_rows, type_is32(c.type) ? 4 : 8)) {
+        if (t->n_rows >= (1ull << 47))
+            return fail(CUBIT_ERR_INVALID, "%llu rows exceed 2^47", (unsigned long long)t->n_rows);
+        if (int rc = ensure_tmp(ctx, padded_words(t->n_rows))) return rc;  // the candidate bitvector
+        const Index& sx = sit->second;
+        SliceSelectArgs g{};
+        g.slices = slice_set(sx);
+        g.n_slices = bits;
+        g.validity = c.validity;
+        g.cand = reinterpret_cast<uint64_t*>(ctx->tmp_ids);
+        g.workspace = ctx->sel;
+        EvalArgs a{};
+        a.prog = em.prog;
+        a.n_rows = t->n_rows;
+        a.n_words = (t->n_rows + 63) / 64;
+        a.row_base = t->row_base;
+        a.ticket = ctx->ticket;
+        a.num_tiles = (uint32_t)((a.n_words + kAggTileWords - 1) / kAggTileWords);
+        if (!live.empty()) {  // zonemap skip: a zone is one tile of the kernels
+            uint32_t n_live = 0;
+            if (int rc = upload_live(ctx, live, 1, &a.live, &n_live)) return rc;
+            a.num_tiles = n_live;
+        }
+        hipEvent_t e0, e1;
+        if (int rc = timing_events(ctx, e0, e1)) return rc;
+        HIP_CHECK(launch_slice_select(a, g, mode, k, q, c.type, sx.vmin, ctx->n_cus, d_out, ctx->stream,
+                                      &t->last_sel_passes, e0, e1));
+        t->last_sel_slices = true;
+        t->last_sliced++;
+        return CUBIT_OK;
+    }
+    // the column path: ids, probed values and their validity words in context scratch
+    const uint64_t cap = t->n_rows;
+    const uint64_t vwords = (cap + 63) / 64;
+    if (int rc = ensure_tmp(ctx, 2 * cap + vwords)) return rc;
+    int64_t* ids = ctx->tmp_ids;
+    int64_t* xv = ctx->tmp_ids + cap;
+    uint64_t* vw = reinterpret_cast<uint64_t*>(ctx->tmp_ids + 2 * cap);
+    uint64_t* count = agg_count_slot(ctx->agg);
+    // (unordered: the decode must not take tmp_ids for an ordering pass)
+    if (int rc = run_eval(ctx, em.prog, t->n_rows, t->row_base, ids, cap, count, nullptr, RunMode::kDecode, true, false,
+                          false, live.empty() ? nullptr : &live, nullptr))
+        return rc;
+    ctx->last_tiles = 0;  // the directory described ids in scratch, not a caller's buffer
+    if (int rc = probe_impl(t, col, txn, ids, count, cap, xv, vw)) return rc;
+    HIP_CHECK(launch_select_arrays(xv, vw, count, cap, mode, k, q, c.type, ctx->sel, d_out, ctx->stream,
+                                   &t->last_sel_passes));
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_last_select(cubit_table* t, int* from_slices, uint32_t* n_passes) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    if (from_slices) *from_slices = t->last_sel_slices ? 1 : 0;
+    if (n_passes) *n_passes = t->last_sel_passes;
+    return CUBIT_OK;
+}
+
+// ORDER BY col [DESC], rowid LIMIT k: the select for rank k - 1, its six numbers read back once, then
+// two ordered scans through the planner with the same txn — the rows strictly before the threshold
+// value and the rows equal to it — merged on the device, the ties cut at the lowest row ids.
+extern "C" int cubit_table_top_n(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_nodes, const cubit_txn* txn,
+                                 int col, uint64_t k, uint32_t flags, int64_t* d_rowids, uint64_t capacity,
+                                 uint64_t* d_count, int64_t* d_out) {
+    if (!t || !d_count || !d_out) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    if (n_nodes && !nodes) return fail(CUBIT_ERR_INVALID, "nodes is null");
+    constexpr uint32_t kPath = CUBIT_SELECT_FROM_SLICES | CUBIT_SELECT_FROM_COLUMN | CUBIT_SELECT_NO_ZONEMAP;
+    if (flags & ~(kPath | CUBIT_SELECT_DESC_ROWS)) return fail(CUBIT_ERR_INVALID, "flags %u", flags);
+    if (k && !d_rowids) return fail(CUBIT_ERR_INVALID, "d_rowids is null");
+    if (capacity < k)
+        return fail(CUBIT_ERR_CAPACITY, "capacity %llu below k = %llu", (unsigned long long)capacity, (unsigned long long)k);
+    auto cit = t->cols.find(col);
+    if (cit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column %d not registered", col);
+    if (cit->second.type == CUBIT_TYPE_VARCHAR || cit->second.dict)
+        return fail(CUBIT_ERR_UNSUPPORTED, "top-N of dictionary column %d: the threshold is a code, not a filter constant", col);
+    if (int rc = set_device(t->ctx)) return rc;
+    cubit_ctx* ctx = t->ctx;
+    if (k == 0) {  // nothing to write
+        HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
+        HIP_CHECK(hipMemsetAsync(d_out, 0, 6 * sizeof(int64_t), ctx->stream));
+        return CUBIT_OK;
+    }
+    const bool desc = (flags & CUBIT_SELECT_DESC_ROWS) != 0;
+    if (int rc = cubit_table_select(t, nodes, n_nodes, txn, col, desc ? CUBIT_SELECT_RANK_DESC : CUBIT_SELECT_RANK, k - 1, 0.0,
+                                    flags & kPath, d_out))
+        return rc;
+    int64_t r[6];
+    HIP_CHECK(hipMemcpyAsync(r, d_out, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const uint32_t scan_flags = CUBIT_SCAN_ORDERED | ((flags & CUBIT_SELECT_NO_ZONEMAP) ? CUBIT_SCAN_NO_ZONEMAP : 0u);
+    // AND(the caller's tree, one more leaf on col)
+    std::vector<cubit_filter_node> tree(n_nodes + 2);
+    tree[0] = cubit_filter_node{CUBIT_FILTER_AND, 0, -1, n_nodes ? 2 : 1, 0};
+    std::copy(nodes, nodes + n_nodes, tree.begin() + 1);
+    cubit_filter_node& leaf = tree[n_nodes + 1];
+    if (!r[1]) {  // fewer than k non-NULL rows qualify: every one of them
+        if (r[4] == 0) {
+            HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
+            return CUBIT_OK;
+        }
+        leaf = cubit_filter_node{CUBIT_FILTER_IS_NOT_NULL, 0, col, 0, 0};
+        return cubit_table_scan(t, tree.data(), n_nodes + 2, txn, d_rowids, capacity, d_count, scan_flags);
+    }
+    const uint64_t n_before = (uint64_t)r[2], n_equal = (uint64_t)r[3], n_ties = k - n_before;
+    int64_t* buf = nullptr;  // the two scans' ids, then their counts
+    if (hipMalloc(&buf, (n_before + n_equal + 2) * sizeof(int64_t)) != hipSuccess)
+        return fail(CUBIT_ERR_OOM, "top-N scratch of %llu ids failed", (unsigned long long)(n_before + n_equal));
+    struct Free {
+        int64_t* p;
+        ~Free() { (void)hipFree(p); }
+    } free_buf{buf};
+    int64_t* before = buf;
+    int64_t* equal = buf + n_before;
+    uint64_t* counts = reinterpret_cast<uint64_t*>(buf + n_before + n_equal);
+    if (n_before) {
+        leaf = cubit_filter_node{CUBIT_FILTER_CONSTANT, desc ? CUBIT_CMP_GT : CUBIT_CMP_LT, col, 0, r[0]};
+        if (int rc = cubit_table_scan(t, tree.data(), n_nodes + 2, txn, before, n_before, counts, scan_flags)) return rc;
+    }
+    leaf = cubit_filter_node{CUBIT_FILTER_CONSTANT, CUBIT_CMP_EQ, col, 0, r[0]};
+    if (int rc = cubit_table_scan(t, tree.data(), n_nodes + 2, txn, equal, n_equal, counts + 1, scan_flags)) return rc;
+    uint64_t got[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(got, counts, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if ((n_before && got[0] != n_before) || got[1] != n_equal)  // the scans see what the select saw
+        return fail(CUBIT_ERR_DEVICE, "top-N scans found %llu + %llu rows, the select %llu + %llu",
+                    (unsigned long long)got[0], (unsigned long long)got[1], (unsigned long long)n_before,
+                    (unsigned long long)n_equal);
+    HIP_CHECK(launch_merge_ids(before, n_before, equal, n_ties, d_rowids, d_count, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));  // buf is freed on return
     return CUBIT_OK;
 }
 

@@ -248,6 +248,46 @@ hipError_t launch_eval_slice_aggregate(EvalArgs a, const SliceAggArgs& g, uint32
 // (bit i, null = all valid), i < min(*d_count, max_n)
 hipError_t launch_aggregate_arrays(const int64_t* x, const uint64_t* valid, const uint64_t* d_count, uint64_t max_n,
                                    uint32_t ops, int type, int64_t* workspace, int64_t* out, hipStream_t stream);
+// Selection by rank (cubit_table_select): a radix select over the column's slices (eval_slice_select,
+// slice_select_narrow: kSelectChunk slices per pass) or over probed values (select_arrays_kernel:
+// kSelectArrayBits bits per pass), one workgroup after each pass summing and walking the histogram
+// (select_step_kernel; the step logic is cubit_program.hpp's). The workspace (kSelectWorkspace int64,
+// allocated on the context by the first select) holds the workgroups' partial histograms — up to
+// kAggMaxGrid × 2^kSelectChunk or kSelectArrayGrid × 2^kSelectArrayBits counters — then the device
+// state and the qualifying-row count. out[0..5] = {value, found, count_below, count_equal,
+// count_valid, count_rows}, ready on the stream with no host round trip.
+constexpr unsigned kSelectArrayGrid = 256;
+constexpr uint64_t kSelectPartials = (uint64_t)kSelectArrayGrid << kSelectArrayBits;
+static_assert(((uint64_t)kAggMaxGrid << kSelectChunk) <= kSelectPartials, "the slice path's partials fit");
+constexpr uint64_t kSelectWorkspace = kSelectPartials + sizeof(SelectState) / sizeof(int64_t) + 2;
+__host__ __device__ inline SelectState* select_state(int64_t* workspace) {
+    return reinterpret_cast<SelectState*>(workspace + kSelectPartials);
+}
+__host__ __device__ inline uint64_t* select_count_slot(int64_t* workspace) {
+    return reinterpret_cast<uint64_t*>(workspace + kSelectPartials + sizeof(SelectState) / sizeof(int64_t));
+}
+struct SliceSelectArgs {
+    SliceSet slices;
+    uint32_t n_slices;
+    const uint64_t* validity;  // as SliceAggArgs'
+    // the candidate bitvector: padded_words(n_rows) words of scratch, 16-byte aligned; the evaluated
+    // tiles' words are written by pass 0 and narrowed in place by the later passes
+    uint64_t* cand;
+    int64_t* workspace;
+};
+// a as launch_eval_slice_aggregate's (a.count is set by the launcher); mode / k / q: CUBIT_SELECT_*, the
+// rank, the quantile; *n_passes (optional) = the passes over the slices
+hipError_t launch_slice_select(EvalArgs a, const SliceSelectArgs& g, int mode, uint64_t k, double q, int type,
+                               int64_t base, int n_cus, int64_t* out, hipStream_t stream, uint32_t* n_passes = nullptr,
+                               hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// the same result from x[i] / valid as launch_aggregate_arrays takes them
+hipError_t launch_select_arrays(const int64_t* x, const uint64_t* valid, const uint64_t* d_count, uint64_t max_n,
+                                int mode, uint64_t k, double q, int type, int64_t* workspace, int64_t* out,
+                                hipStream_t stream, uint32_t* n_passes = nullptr);
+// out[0 … na + nb) = the ascending merge of two ascending runs of distinct row ids (cubit_table_top_n);
+// *count = na + nb
+hipError_t launch_merge_ids(const int64_t* a, uint64_t na, const int64_t* b, uint64_t nb, int64_t* out, uint64_t* count,
+                            hipStream_t stream);
 // The grouped forms (cubit_table_aggregate_grouped). Either kernel leaves kGroupPartial int64 per
 // group and workgroup in `partials`, group-major ([slot][workgroup]) — {Σ lo, Σ hi, smallest offset,
 // largest offset, valid rows, rows} — and one finishing wave per group combines them as above

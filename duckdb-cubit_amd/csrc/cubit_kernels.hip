@@ -2530,6 +2530,292 @@ __global__ __launch_bounds__(64) void aggregate_finish_kernel(const int64_t* __r
     }
 }
 
+// Select: the k-th smallest / largest value (or quantile_disc) of the column over the rows a program
+// keeps, from the slices alone — a radix select over the offsets, most significant slices first,
+// kSelectChunk slices per pass (cubit_program.hpp has the step logic, shared with the CPU).
+//   pass 0     eval_slice_select, in the eval_* family as eval_slice_aggregate: F in registers,
+//              C = F ∧ valid written to the candidate bitvector (every word of every evaluated tile),
+//              count_rows through the ticket, and the first chunk histogrammed: per pair of words
+//              the popcounts of the 2^cnt AND-combinations of C with the chunk's slices and their
+//              complements, formed depth-first so one mask per level is live;
+//   pass p > 0 slice_select_narrow reads C, loads the previous chunk again and the next one (all
+//              loads before use), keeps the rows whose previous chunk equals the bucket the step
+//              chose (read from the device state; uniform), writes C back in place (one thread per
+//              word) and histograms the next chunk.
+// After each pass one workgroup (select_step_kernel) sums the workgroups' partial histograms and applies
+// select_step; after the last it writes the six result slots. The chosen bucket's count after the
+// last chunk is count_equal, so the candidates are not narrowed by the last chunk. Counters are
+// exact 64-bit integers reduced by wave, then workgroup, then per-workgroup partials: no atomics per
+// row, no workgroup waits on another, the stream orders the passes. A pair whose C is zero across
+// the wave skips its slice loads. Traffic: (K [+ 1] + 1 + 2b - d_last + 2·(passes - 1))·n/8 bytes
+// over the live zones.
+template <int CNT, int J, int IDX>
+__device__ __forceinline__ void select_hist_rec(const u64x2 (&w)[CNT > 0 ? CNT : 1], const u64x2& x, uint32_t px,
+                                                uint64_t (&h)[1 << kSelectChunk]) {
+    if constexpr (J == CNT) {
+        h[IDX] += px;
+    } else {
+        const u64x2 one = x & w[J];
+        const uint32_t p1 = (uint32_t)(__popcll(one.x) + __popcll(one.y));
+        select_hist_rec<CNT, J + 1, 2 * IDX + 1>(w, one, p1, h);
+        const u64x2 zero = x & ~w[J];
+        select_hist_rec<CNT, J + 1, 2 * IDX>(w, zero, px - p1, h);
+    }
+}
+// the chunk whose top slice is `top` (w[0]), CNT slices: bucket = the chunk's bits, top slice first
+template <int CNT>
+__device__ __forceinline__ void select_hist_chunk(const SliceSet& sl, int top, uint64_t pi, const u64x2& c,
+                                                  uint64_t (&h)[1 << kSelectChunk]) {
+    u64x2 w[CNT > 0 ? CNT : 1];
+#pragma unroll
+    for (int j = 0; j < CNT; ++j) w[j] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(sl.s[top - j]) + pi);
+    select_hist_rec<CNT, 0, 0>(w, c, (uint32_t)(__popcll(c.x) + __popcll(c.y)), h);
+}
+
+// wave, then workgroup, then this workgroup's partials (nb counters at workspace + nb·blockIdx.x)
+template <int NWAVES>
+__device__ __forceinline__ void select_hist_publish(uint64_t (&h)[1 << kSelectChunk], int64_t* workspace, int t) {
+    constexpr int NB = 1 << kSelectChunk;
+    __shared__ uint64_t s_hist[NWAVES][NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) h[i] = wave_sum(h[i]);
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) s_hist[t >> 6][i] = h[i];
+    }
+    __syncthreads();
+    if (t < NB) {
+        uint64_t s = 0;
+        for (int w = 0; w < NWAVES; ++w) s += s_hist[w][t];
+        workspace[(uint64_t)NB * blockIdx.x + t] = (int64_t)s;
+    }
+}
+
+template <int K, int FORM>
+__global__ __launch_bounds__(512, 2) void eval_slice_select(EvalArgs a, SliceSelectArgs g) {
+    constexpr int THREADS = 512, PAIRS = 2, NW = 4;
+    constexpr uint64_t TILE_WORDS = (uint64_t)THREADS * NW;
+    static_assert(TILE_WORDS == kAggTileWords, "a tile is one zone");
+    constexpr int NWAVES = THREADS / 64;
+    const int t = threadIdx.x;
+    uint64_t c_rows = 0;
+    uint64_t h[1 << kSelectChunk];
+#pragma unroll
+    for (int i = 0; i < (1 << kSelectChunk); ++i) h[i] = 0;
+    const int cnt0 = (int)select_first_chunk(g.n_slices, kSelectChunk), top = (int)g.n_slices - 1;
+    const uint32_t n_idx = a.num_tiles;
+    for (uint32_t i = blockIdx.x; i < n_idx; i += gridDim.x) {
+        const uint64_t tile_word0 = (uint64_t)tile_at(a, i) * TILE_WORDS;
+        uint64_t r[NW];
+        if constexpr (K > 0) {
+            u64x2 v[K][PAIRS];
+            load_tile<K, PAIRS, THREADS>(a, tile_word0, t, v);
+            eval_words<K, NW, FORM>(a.prog, v, r);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) r[j] = ~0ull;
+        }
+        tail_mask<NW, THREADS>(a, tile_word0, t, r);
+        u64x2 fv[PAIRS];
+#pragma unroll
+        for (int p = 0; p < PAIRS; ++p) {
+            fv[p].x = r[2 * p];
+            fv[p].y = r[2 * p + 1];
+        }
+        if (g.validity) {
+            if (tile_word0 + TILE_WORDS <= a.n_words) {  // uniform: the whole tile lies below the last word
+#pragma unroll
+                for (int p = 0; p < PAIRS; ++p)
+                    fv[p] &= reinterpret_cast<const u64x2*>(g.validity + tile_word0)[p * THREADS + t];
+            } else {  // the tile holding the last word: nothing at or past n_words is read
+#pragma unroll
+                for (int p = 0; p < PAIRS; ++p) {
+                    const uint64_t gw = word_index<THREADS>(tile_word0, 2 * p, t);
+                    fv[p].x &= gw < a.n_words ? g.validity[gw] : 0ull;
+                    fv[p].y &= gw + 1 < a.n_words ? g.validity[gw + 1] : 0ull;
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < PAIRS; ++p) {
+            c_rows += (uint64_t)(__popcll(r[2 * p]) + __popcll(r[2 * p + 1]));
+            const u64x2 c = fv[p];
+            const uint64_t pi = (tile_word0 >> 1) + (uint64_t)(p * THREADS + t);
+            reinterpret_cast<u64x2*>(g.cand)[pi] = c;  // the tile lies inside the padded candidate words
+            if (__ballot((c.x | c.y) != 0) == 0) continue;  // no candidate in the wave's 128 words
+            switch (cnt0) {  // uniform
+            case 1: select_hist_chunk<1>(g.slices, top, pi, c, h); break;
+            case 2: select_hist_chunk<2>(g.slices, top, pi, c, h); break;
+            case 3: select_hist_chunk<3>(g.slices, top, pi, c, h); break;
+            case 4: select_hist_chunk<4>(g.slices, top, pi, c, h); break;
+            default: select_hist_chunk<0>(g.slices, top, pi, c, h); break;  // no slice: one bucket, the rows
+            }
+        }
+    }
+    select_hist_publish<NWAVES>(h, g.workspace, t);
+    c_rows = wave_sum(c_rows);
+    __shared__ uint64_t s_rows[NWAVES];
+    if ((t & 63) == 0) s_rows[t >> 6] = c_rows;
+    __syncthreads();
+    if (t == 0) {
+        uint64_t cr = 0;
+        for (int w = 0; w < NWAVES; ++w) cr += s_rows[w];
+        finish_ticket(a.ticket, a.count, cr);
+    }
+}
+
+// PC: the previous chunk's slices (its lowest at prev_low); the next chunk is whole, its lowest slice
+// at prev_low - kSelectChunk. a: the tile list of pass 0 (num_tiles, live).
+template <int PC>
+__global__ __launch_bounds__(512, 2) void slice_select_narrow(EvalArgs a, SliceSelectArgs g, uint32_t prev_low) {
+    constexpr int THREADS = 512, PAIRS = 2, NW = 4, NC = (int)kSelectChunk;
+    constexpr uint64_t TILE_WORDS = (uint64_t)THREADS * NW;
+    constexpr int NWAVES = THREADS / 64;
+    const int t = threadIdx.x;
+    uint64_t h[1 << kSelectChunk];
+#pragma unroll
+    for (int i = 0; i < (1 << kSelectChunk); ++i) h[i] = 0;
+    const SelectState* st = select_state(g.workspace);
+    if (st->found) {  // uniform; a select without a row leaves the candidates and the histogram alone
+        const uint32_t want = (uint32_t)(st->prefix >> prev_low);  // the previous chunk's bucket in its low PC bits
+        const int ptop = (int)prev_low + PC - 1, ntop = (int)prev_low - 1;
+        const uint32_t n_idx = a.num_tiles;
+        for (uint32_t i = blockIdx.x; i < n_idx; i += gridDim.x) {
+            const uint64_t tile_word0 = (uint64_t)tile_at(a, i) * TILE_WORDS;
+#pragma unroll
+            for (int p = 0; p < PAIRS; ++p) {
+                const uint64_t pi = (tile_word0 >> 1) + (uint64_t)(p * THREADS + t);
+                u64x2 c = reinterpret_cast<const u64x2*>(g.cand)[pi];
+                if (__ballot((c.x | c.y) != 0) == 0) continue;  // no candidate in the wave's 128 words
+                u64x2 pw[PC], w[NC];
+#pragma unroll
+                for (int j = 0; j < PC; ++j)
+                    pw[j] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(g.slices.s[ptop - j]) + pi);
+#pragma unroll
+                for (int j = 0; j < NC; ++j)
+                    w[j] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(g.slices.s[ntop - j]) + pi);
+#pragma unroll
+                for (int j = 0; j < PC; ++j) {
+                    if ((want >> (PC - 1 - j)) & 1u) c &= pw[j];
+                    else c &= ~pw[j];
+                }
+                reinterpret_cast<u64x2*>(g.cand)[pi] = c;
+                select_hist_rec<NC, 0, 0>(w, c, (uint32_t)(__popcll(c.x) + __popcll(c.y)), h);
+            }
+        }
+    }
+    select_hist_publish<NWAVES>(h, g.workspace, t);
+}
+
+// The array select's pass (the column path): x / valid / d_count as aggregate_arrays_kernel reads
+// them. A row's comparison key ^ 2^63 orders unsigned (an offset from base INT64_MIN); the pass
+// histograms bits [shift, shift + 8) of the rows whose higher bits equal the state's prefix into 256
+// LDS counters per workgroup and leaves them as the workgroup's partials.
+__global__ __launch_bounds__(256) void select_arrays_kernel(const int64_t* __restrict__ x,
+                                                            const uint64_t* __restrict__ valid,
+                                                            const uint64_t* __restrict__ d_count, uint64_t max_n,
+                                                            int type, uint32_t shift, int first,
+                                                            int64_t* __restrict__ workspace) {
+    constexpr int NB = 1 << kSelectArrayBits;
+    static_assert(NB == 256, "one counter per thread");
+    __shared__ unsigned long long s_h[NB];
+    s_h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t n = min(*d_count, max_n);
+    const SelectState* st = select_state(workspace);
+    if (first || st->found) {  // uniform
+        // (the first pass takes every valid row: the state is not set yet)
+        const uint64_t hi_mask = first ? 0ull : ~0ull << (shift + kSelectArrayBits);
+        const uint64_t prefix = first ? 0ull : st->prefix & hi_mask;
+        const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+        const uint32_t lane = threadIdx.x & 63u;
+        // a wave walks 64 consecutive rows with every lane active (the bound is on the wave's first
+        // row), so the ballots below see the whole wave
+        for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += stride) {
+            const uint64_t i = i0 + lane;
+            bool take = i < n && (!valid || ((valid[i0 >> 6] >> lane) & 1ull));
+            uint32_t bucket = 0;
+            if (take) {
+                const uint64_t off = (uint64_t)value_key(type, x[i]) ^ 0x8000000000000000ull;
+                take = (off & hi_mask) == prefix;
+                bucket = (uint32_t)(off >> shift) & (NB - 1);
+            }
+            const uint64_t m = __ballot(take);
+            if (m == 0) continue;
+            // a wave whose rows all fall into one bucket (the passes above a narrow column's span,
+            // heavy ties) adds its count once: 64 atomics on one LDS address serialise
+            const uint32_t lead = (uint32_t)__shfl((int)bucket, __ffsll((unsigned long long)m) - 1, 64);
+            if (__ballot(take && bucket == lead) == m) {
+                if (lane == 0) atomicAdd(&s_h[lead], (unsigned long long)__popcll(m));
+            } else if (take) {
+                atomicAdd(&s_h[bucket], 1ull);
+            }
+        }
+    }
+    __syncthreads();
+    workspace[(uint64_t)NB * blockIdx.x + threadIdx.x] = (int64_t)s_h[threadIdx.x];
+    if (first && blockIdx.x == 0 && threadIdx.x == 0) *select_count_slot(workspace) = n;  // count_rows
+}
+
+// One workgroup after each pass: sums the nblocks partial histograms of nb buckets (a power of two,
+// at most 256) — thread t takes bucket t mod nb of every (1024 / nb)-th workgroup, so the loads of
+// one bucket spread over 4 … 1024 threads and a lane issues nblocks·nb/1024 of them — and thread 0
+// applies select_step to the device state; `last` writes the six result slots.
+constexpr int kSelectStepThreads = 1024;
+__global__ __launch_bounds__(kSelectStepThreads) void select_step_kernel(int64_t* __restrict__ workspace, int nblocks,
+                                                                         uint32_t nb, uint32_t low, int first, int last,
+                                                                         int mode, uint64_t k, double q, int type,
+                                                                         int64_t base, int64_t* __restrict__ out) {
+    __shared__ uint64_t s_part[kSelectStepThreads];
+    __shared__ uint64_t s_counts[1 << kSelectArrayBits];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t groups = (uint32_t)kSelectStepThreads / nb, j = lane % nb;
+    uint64_t sum = 0;
+    for (uint32_t b = lane / nb; b < (uint32_t)nblocks; b += groups) sum += (uint64_t)workspace[(uint64_t)nb * b + j];
+    s_part[lane] = sum;
+    __syncthreads();
+    if (lane < nb) {
+        uint64_t c = 0;
+        for (uint32_t g = 0; g < groups; ++g) c += s_part[g * nb + lane];
+        s_counts[lane] = c;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        SelectState* st = select_state(workspace);
+        SelectState state = *st;
+        select_step(&state, first != 0, mode, k, q, s_counts, nb, low);
+        *st = state;
+        if (last) {
+            int64_t r[6];
+            select_result(state, type, base, *select_count_slot(workspace), r);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) out[i] = r[i];
+        }
+    }
+}
+
+// Two ascending runs of distinct row ids (no id in both) merged into one: every element lands at its
+// index plus the number of the other run's ids below it (a binary search). *count = na + nb.
+__device__ __forceinline__ uint64_t ids_below(const int64_t* __restrict__ v, uint64_t n, int64_t x) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (v[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(256) void merge_ids_kernel(const int64_t* __restrict__ a, uint64_t na,
+                                                        const int64_t* __restrict__ b, uint64_t nb,
+                                                        int64_t* __restrict__ out, uint64_t* __restrict__ count) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < na + nb; i += stride) {
+        if (i < na) out[i + ids_below(b, nb, a[i])] = a[i];
+        else out[(i - na) + ids_below(a, na, b[i - na])] = b[i - na];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count = na + nb;
+}
+
 // GROUP BY: eval_slice_aggregate over a batch of groups per launch. Each group is the AND of one
 // equality bitvector per group column, so the tile walk, the program evaluation and the slice stream
 // are eval_slice_aggregate's, read once for the whole batch, and per pair of words the batch's group
@@ -4676,6 +4962,72 @@ hipError_t launch_aggregate_arrays(const int64_t* x, const uint64_t* valid, cons
                        workspace);
     hipLaunchKernelGGL(aggregate_finish_kernel, dim3(1), dim3(64), 0, stream, workspace, (int)grid, ops, type,
                        (int64_t)0, 0, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_slice_select(EvalArgs a, const SliceSelectArgs& g, int mode, uint64_t k, double q, int type,
+                               int64_t base, int n_cus, int64_t* out, hipStream_t stream, uint32_t* n_passes,
+                               hipEvent_t ev0, hipEvent_t ev1) {
+    if (g.n_slices > kMaxSlices || a.num_tiles == 0 || !g.workspace || !g.cand || !a.ticket) return hipErrorInvalidValue;
+    a.count = select_count_slot(g.workspace);
+    // persistent grid, as the aggregate's: two 512-thread workgroups per CU
+    const unsigned grid =
+        std::max(1u, std::min<unsigned>(a.num_tiles, std::min<unsigned>(2u * (unsigned)n_cus, kAggMaxGrid)));
+    const uint32_t bits = g.n_slices, passes = select_passes(bits, kSelectChunk);
+    if (n_passes) *n_passes = passes;
+    hipError_t e = hipSuccess;
+    if (a.prog.n_leaves == 0)
+        hipExtLaunchKernelGGL((eval_slice_select<0, FORM_CONJ>), dim3(grid), dim3(512), 0, stream, ev0, nullptr, 0, a, g);
+    else
+        e = dispatch_k_form(a.prog, [&](auto kk, auto form) {
+            hipExtLaunchKernelGGL((eval_slice_select<kk.value, form.value>), dim3(grid), dim3(512), 0, stream, ev0,
+                                  nullptr, 0, a, g);
+        });
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    for (uint32_t p = 0; p < passes; ++p) {
+        const uint32_t low = select_chunk_low(bits, kSelectChunk, p);
+        if (p > 0) {
+            const uint32_t pc = select_chunk_bits(bits, kSelectChunk, p - 1), plow = select_chunk_low(bits, kSelectChunk, p - 1);
+#define CUBIT_NARROW(PC) \
+    hipLaunchKernelGGL((slice_select_narrow<PC>), dim3(grid), dim3(512), 0, stream, a, g, plow)
+            if (pc == 1) CUBIT_NARROW(1);
+            else if (pc == 2) CUBIT_NARROW(2);
+            else if (pc == 3) CUBIT_NARROW(3);
+            else CUBIT_NARROW(4);
+#undef CUBIT_NARROW
+        }
+        const bool last = p + 1 == passes;
+        // (the partials hold 2^kSelectChunk counters per workgroup whatever the chunk; those past
+        // 2^cnt are zero)
+        hipExtLaunchKernelGGL(select_step_kernel, dim3(1), dim3(kSelectStepThreads), 0, stream, nullptr, last ? ev1 : nullptr, 0,
+                              g.workspace, (int)grid, 1u << kSelectChunk, low, p == 0 ? 1 : 0, last ? 1 : 0, mode, k, q,
+                              type, base, out);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_select_arrays(const int64_t* x, const uint64_t* valid, const uint64_t* d_count, uint64_t max_n,
+                                int mode, uint64_t k, double q, int type, int64_t* workspace, int64_t* out,
+                                hipStream_t stream, uint32_t* n_passes) {
+    if (!workspace) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((max_n + 2047) / 2048, kSelectArrayGrid));
+    constexpr uint32_t passes = 64 / kSelectArrayBits;
+    if (n_passes) *n_passes = passes;
+    for (uint32_t p = 0; p < passes; ++p) {
+        const uint32_t shift = 64 - (p + 1) * kSelectArrayBits;
+        hipLaunchKernelGGL(select_arrays_kernel, dim3(grid), dim3(256), 0, stream, x, valid, d_count, max_n, type, shift,
+                           p == 0 ? 1 : 0, workspace);
+        hipLaunchKernelGGL(select_step_kernel, dim3(1), dim3(kSelectStepThreads), 0, stream, workspace, (int)grid, 1u << kSelectArrayBits,
+                           shift, p == 0 ? 1 : 0, p + 1 == passes ? 1 : 0, mode, k, q, type, INT64_MIN, out);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_ids(const int64_t* a, uint64_t na, const int64_t* b, uint64_t nb, int64_t* out, uint64_t* count,
+                            hipStream_t stream) {
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((na + nb + 255) / 256, 4096));
+    hipLaunchKernelGGL(merge_ids_kernel, dim3(grid), dim3(256), 0, stream, a, na, b, nb, out, count);
     return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <utility>
@@ -323,6 +324,137 @@ inline bool grouped_from_slices(bool force_slices, bool force_column, bool usabl
     double column = (double)k_leaves / 8.0 * (double)live_rows + 16.0 * (double)est_rows;
     for (uint32_t i = 0; i < n_probed; ++i)
         column += 16.0 * (double)est_rows + std::min(128.0 * (double)est_rows, (double)elem_bytes[i] * (double)rows);
+    return slices <= column;
+}
+
+// ---- selection by rank from a bit-sliced index (cubit_table_select; O'Neil & Quass 1997 §3)
+//
+// A radix select over the offsets u = key - base, most significant slices first. A step histograms
+// one chunk of slices over the candidate rows (the filter's non-NULL rows whose higher bits equal the
+// prefix chosen so far), walks the buckets to the one that holds the rank still sought, and appends
+// that bucket to the prefix. The step logic below runs on the device (select_step_kernel,
+// cubit_kernels.hip) and on the CPU (tests/slice_select_core.cpp).
+constexpr int kSelectRank = CUBIT_SELECT_RANK, kSelectRankDesc = CUBIT_SELECT_RANK_DESC, kSelectQuantile = CUBIT_SELECT_QUANTILE;
+// slices per pass of the slice select (2^d buckets per thread) and bits per pass of the array select
+constexpr uint32_t kSelectChunk = 4;
+constexpr uint32_t kSelectArrayBits = 8;
+
+// The 0-based ascending rank quantile_disc(col, q) returns among n values, q a double in [0, 1]
+// (the reference's Interpolator<true>::Index for a non-DECIMAL q,
+// src/include/duckdb/core_functions/aggregate/quantile_sort_tree.hpp:166-188), in the same double
+// arithmetic on the device as on the host: the product is rounded before the subtraction (no fused
+// multiply-add). n = 0 gives 0, which is no row.
+CUBIT_HD inline uint64_t quantile_disc_index(uint64_t n, double q) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double scaled_q = (double)n * q;
+    const uint64_t floored = (uint64_t)floor((double)n - scaled_q);
+    const uint64_t left = n - floored;
+    return (left > 1 ? left : 1) - 1;
+}
+
+// The chunks of a select over `bits` slices, most significant first: the first takes bits mod d
+// slices when that is non-zero, so every later chunk is whole. With no slice one pass still runs
+// (it counts the rows; its single bucket is the base).
+CUBIT_HD inline uint32_t select_passes(uint32_t bits, uint32_t d) { return bits ? (bits + d - 1) / d : 1; }
+CUBIT_HD inline uint32_t select_first_chunk(uint32_t bits, uint32_t d) { return bits % d ? bits % d : (bits ? d : 0); }
+// the slices of chunk p (0-based): count and lowest slice
+CUBIT_HD inline uint32_t select_chunk_bits(uint32_t bits, uint32_t d, uint32_t p) {
+    return p == 0 ? select_first_chunk(bits, d) : d;
+}
+CUBIT_HD inline uint32_t select_chunk_low(uint32_t bits, uint32_t d, uint32_t p) {
+    return bits ? bits - select_first_chunk(bits, d) - p * d : 0;
+}
+
+// The bucket walk of one radix step. counts: nb bucket counts, bucket i = the rows whose chunk bits
+// are i; desc walks them from the top. rank: the 0-based rank still sought among those rows in the
+// walk's direction. Finds the bucket that holds it, the rank inside that bucket and the rows the
+// step ruled out before it (the buckets walked past). False — nothing written — when rank is at or
+// past the total.
+CUBIT_HD inline bool select_walk(const uint64_t* counts, uint32_t nb, bool desc, uint64_t rank, uint32_t* bucket,
+                                 uint64_t* rank_in, uint64_t* ruled_out) {
+    uint64_t before = 0;
+    for (uint32_t i = 0; i < nb; ++i) {
+        const uint32_t b = desc ? nb - 1 - i : i;
+        if (rank - before < counts[b]) {
+            *bucket = b;
+            *rank_in = rank - before;
+            *ruled_out = before;
+            return true;
+        }
+        before += counts[b];
+    }
+    return false;
+}
+
+// The select's device state, carried from step to step on the stream.
+struct SelectState {
+    uint64_t prefix;       // the offset's bits chosen so far, at their place in the offset
+    uint64_t rank;         // the rank still sought inside the prefix's rows
+    uint64_t below;        // rows ruled out before the value in the direction asked
+    uint64_t equal;        // rows inside the prefix
+    uint64_t found;        // 0: no such row (every later step leaves the state alone)
+    uint64_t count_valid;  // the filter's non-NULL rows
+};
+// One step: `first` turns mode / k / q and the first histogram's total into the rank; low = the
+// chunk's lowest bit in the offset.
+CUBIT_HD inline void select_step(SelectState* s, bool first, int mode, uint64_t k, double q, const uint64_t* counts,
+                                 uint32_t nb, uint32_t low) {
+    if (first) {
+        uint64_t total = 0;
+        for (uint32_t i = 0; i < nb; ++i) total += counts[i];
+        s->prefix = s->below = s->equal = 0;
+        s->count_valid = total;
+        s->rank = mode == kSelectQuantile ? quantile_disc_index(total, q) : k;
+        s->found = s->rank < total ? 1 : 0;
+    }
+    if (!s->found) return;
+    uint32_t bucket = 0;
+    uint64_t rank_in = 0, out = 0;
+    if (!select_walk(counts, nb, mode == kSelectRankDesc, s->rank, &bucket, &rank_in, &out)) {
+        s->found = 0;  // (the histograms of one select always hold the rank: not reached)
+        return;
+    }
+    s->prefix |= (uint64_t)bucket << low;
+    s->rank = rank_in;
+    s->below += out;
+    s->equal = counts[bucket];
+}
+// the six result slots {value, found, count_below, count_equal, count_valid, count_rows}: the value
+// mapped from the offset as slice_agg_combine maps MIN / MAX
+CUBIT_HD inline void select_result(const SelectState& s, int type, int64_t base, uint64_t count_rows, int64_t out[6]) {
+    out[0] = s.found ? agg_key_value(type, (int64_t)((uint64_t)base + s.prefix)) : 0;
+    out[1] = (int64_t)s.found;
+    out[2] = s.found ? (int64_t)s.below : 0;
+    out[3] = s.found ? (int64_t)s.equal : 0;
+    out[4] = (int64_t)s.count_valid;
+    out[5] = (int64_t)count_rows;
+}
+
+// Which path cubit_table_select takes, shaped like aggregate_from_slices: the slices (true) or scan +
+// probe + array select. By estimated bytes alone:
+//   slices: pass 0 reads the K leaves, the validity and its chunk and writes the candidates; each
+//           later pass reads and writes the candidates, reads the previous chunk again and the next:
+//           (K + nullable + 1 + 2b - d + 2·(passes - 1))/8 bytes per live row, d = the last chunk;
+//   column: the aggregate's scan + probe (K/8 per live row; 32 bytes and one 128-byte line per
+//           estimated qualifying row, never more lines than the column has), then 64/kSelectArrayBits
+//           passes over the probed values (8 bytes each).
+// The constants are derived from bytes alone and marked so: at 612 M rows (scripts/slice_select_timing.py,
+// DESIGN.md §3) the rule's crossover is 1.4 % of the rows for 12 slices and 3.1 % for 24, while the
+// slices measured faster from 1 % up (and slower at 1e-3): the array passes run well below the memory
+// rate the model charges them. Correctness never depends on the choice.
+inline bool select_from_slices(bool force_slices, bool force_column, bool usable, uint32_t bits, uint32_t k_leaves,
+                               bool nullable, uint64_t live_rows, uint64_t rows, uint64_t est_rows, uint64_t elem_bytes) {
+    if (force_column || !usable) return false;
+    if (force_slices) return true;
+    const uint32_t passes = select_passes(bits, kSelectChunk);
+    const uint32_t last = select_chunk_bits(bits, kSelectChunk, passes - 1);
+    const double per_row = (double)(k_leaves + (nullable ? 1u : 0u) + 1u + 2u * bits - last + 2u * (passes - 1));
+    const double slices = per_row / 8.0 * (double)live_rows;
+    const double gathered = std::min(128.0 * (double)est_rows, (double)elem_bytes * (double)rows);
+    const double column = (double)k_leaves / 8.0 * (double)live_rows + 32.0 * (double)est_rows + gathered +
+                          8.0 * (double)(64 / kSelectArrayBits) * (double)est_rows;
     return slices <= column;
 }
 

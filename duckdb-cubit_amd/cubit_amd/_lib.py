@@ -59,6 +59,9 @@ AGG_SUM, AGG_MIN, AGG_MAX = 1, 2, 4
 AGG_ALL = AGG_SUM | AGG_MIN | AGG_MAX
 AGG_FROM_SLICES, AGG_FROM_COLUMN, AGG_NO_ZONEMAP = 16, 32, 64
 AGG_MAX_GROUP_COLS, AGG_MAX_GROUPS = 2, 256
+SELECT_RANK, SELECT_RANK_DESC, SELECT_QUANTILE = 0, 1, 2
+SELECT_DESC_ROWS = 1
+SELECT_FROM_SLICES, SELECT_FROM_COLUMN, SELECT_NO_ZONEMAP = 16, 32, 64
 OP_AND, OP_OR, OP_ANDNOT = -1, -2, -3
 SCAN_COUNT_ONLY = 1
 SCAN_ORDERED = 2
@@ -206,6 +209,10 @@ GPU_SIGNATURES = {
     "cubit_table_aggregate_grouped": (C.c_int, [_P, _P, _U32, _P, C.c_int, _P, _U32, _U32, _P, _U32]),
     "cubit_table_last_grouped": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(_U32), C.POINTER(_U32)]),
     "cubit_bitslice_aggregate": (C.c_int, [_P, _P, _U32, _P, _P, _U64, C.c_int, _I64, _U32, _P]),
+    "cubit_table_select": (C.c_int, [_P, _P, _U32, _P, C.c_int, C.c_int, _U64, C.c_double, _U32, _P]),
+    "cubit_table_last_select": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(_U32)]),
+    "cubit_bitslice_select": (C.c_int, [_P, _P, _U32, _P, _P, _U64, C.c_int, _I64, C.c_int, _U64, C.c_double, _P]),
+    "cubit_table_top_n": (C.c_int, [_P, _P, _U32, _P, C.c_int, _U64, _U32, _P, _U64, _P, _P]),
     "cubit_table_column_data": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int)]),
     "cubit_table_set_inserts": (C.c_int, [_P, _P, _P, _P, _U64]),
     "cubit_table_append": (C.c_int, [_P, _U64, _P, _P, _P, C.c_uint32, _U64]),

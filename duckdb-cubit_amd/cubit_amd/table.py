@@ -242,6 +242,19 @@ class Aggregate(NamedTuple):
     count_rows: int
 
 
+class Selected(NamedTuple):
+    """CubitTable.quantile's and kth's result: value in column_statistics' form (None when not
+    found), the qualifying non-NULL rows strictly before it in the direction asked and equal to it,
+    and aggregate's two counts."""
+
+    value: Optional[int]
+    found: bool
+    below: int
+    equal: int
+    count_valid: int
+    count_rows: int
+
+
 class CubitTable:
     """A row-range partition [row_base, row_base + n_rows) resident on one device."""
 
@@ -663,6 +676,97 @@ class CubitTable:
         v = C.c_int()
         L.check(self.lib.cubit_table_last_aggregate(self.handle, C.byref(v)))
         return bool(v.value)
+
+    def _select(self, col, mode, k, q, filter_set, residual, txn, path, zonemap) -> "Selected":
+        if path not in (None, "slices", "column"):
+            raise ValueError(f"path {path!r}")
+        flags = {None: 0, "slices": L.SELECT_FROM_SLICES, "column": L.SELECT_FROM_COLUMN}[path]
+        flags |= 0 if zonemap else L.SELECT_NO_ZONEMAP
+        plan = serialize(filter_set, residual)
+        arr = to_ctypes(plan.nodes)
+        out = self.ctx.alloc(48)
+        try:
+            L.check(self.lib.cubit_table_select(self.handle, arr, len(plan.nodes),
+                                                C.byref(txn) if txn is not None else None, col, mode, int(k),
+                                                float(q), flags, C.c_void_p(out.addr)))
+            self.ctx.check()
+            v, found, below, equal, cv, cr = (int(x) for x in out.download(np.int64, 6))
+        finally:
+            out.free()
+        return Selected(v if found else None, bool(found), below, equal, cv, cr)
+
+    def quantile(self, col: int, q: float, filter_set: Optional[TableFilterSet] = None,
+                 residual: Optional[Residual] = None, txn: Optional[L.Txn] = None, path: Optional[str] = None,
+                 zonemap: bool = True) -> "Selected":
+        """SELECT quantile_disc(col, q) WHERE <filter> → Selected, the value decoded as aggregate()
+        decodes min / max. NULLs are ignored. path and zonemap as aggregate()'s."""
+        return self._select(col, L.SELECT_QUANTILE, 0, q, filter_set, residual, txn, path, zonemap)
+
+    def kth(self, col: int, k: int, desc: bool = False, filter_set: Optional[TableFilterSet] = None,
+            residual: Optional[Residual] = None, txn: Optional[L.Txn] = None, path: Optional[str] = None,
+            zonemap: bool = True) -> "Selected":
+        """The value of 0-based rank k among the qualifying non-NULL rows, ascending or (desc) from
+        the largest → Selected (found False when k >= count_valid)."""
+        return self._select(col, L.SELECT_RANK_DESC if desc else L.SELECT_RANK, k, 0.0, filter_set, residual, txn,
+                            path, zonemap)
+
+    def last_select(self):
+        """(whether the last quantile() / kth() / top_n() read the bit slices, its passes over the
+        slices or the probed values)."""
+        f, n = C.c_int(), C.c_uint32()
+        L.check(self.lib.cubit_table_last_select(self.handle, C.byref(f), C.byref(n)))
+        return bool(f.value), int(n.value)
+
+    def top_n(self, col: int, k: int, desc: bool = False, filter_set: Optional[TableFilterSet] = None,
+              residual: Optional[Residual] = None, txn: Optional[L.Txn] = None, path: Optional[str] = None,
+              zonemap: bool = True, capacity: Optional[int] = None, sort: bool = True):
+        """… WHERE <filter> ORDER BY col [DESC], rowid LIMIT k over the non-NULL rows →
+        (row ids, values, Selected of rank k - 1): the ids as the library hands them out (ascending)
+        re-ordered here by (value, row id) — descending values with desc — after a probe of the at
+        most k rows (sort=False: as the library wrote them). capacity: the id buffer's size (default k)."""
+        if path not in (None, "slices", "column"):
+            raise ValueError(f"path {path!r}")
+        flags = {None: 0, "slices": L.SELECT_FROM_SLICES, "column": L.SELECT_FROM_COLUMN}[path]
+        flags |= (0 if zonemap else L.SELECT_NO_ZONEMAP) | (L.SELECT_DESC_ROWS if desc else 0)
+        cap = int(k) if capacity is None else int(capacity)
+        plan = serialize(filter_set, residual)
+        arr = to_ctypes(plan.nodes)
+        ids, cnt, out = self.ctx.alloc(max(cap, 1) * 8), self.ctx.alloc(16), self.ctx.alloc(48)
+        try:
+            L.check(self.lib.cubit_table_top_n(self.handle, arr, len(plan.nodes),
+                                               C.byref(txn) if txn is not None else None, col, int(k), flags,
+                                               C.c_void_p(ids.addr), cap, C.c_void_p(cnt.addr), C.c_void_p(out.addr)))
+            self.ctx.check()
+            n = int(cnt.download(np.uint64, 1)[0])
+            rows = ids.download(np.int64, n)
+            v, found, below, equal, cv, cr = (int(x) for x in out.download(np.int64, 6))
+        finally:
+            for b in (ids, cnt, out):
+                b.free()
+        sel = Selected(v if found else None, bool(found), below, equal, cv, cr)
+        if n == 0:
+            return rows, np.empty(0, dtype=np.int64), sel
+        vals, _ = self.fetch(col, rows, txn)
+        if not sort:
+            return rows, vals, sel
+        keys = self._order_keys(col, vals)
+        order = np.lexsort((rows, ~keys if desc else keys))  # ~: descending without overflow
+        return rows[order], vals[order], sel
+
+    def _order_keys(self, col: int, vals: np.ndarray) -> np.ndarray:
+        """int64 keys that order a column's probed values as the library compares them (FLOAT /
+        DOUBLE patterns through their order key: NaN greatest, -0.0 = +0.0; UINT64 bits unsigned)."""
+        type_ = self.types.get(col)
+        if type_ == L.TYPE_FLOAT:
+            u = vals.astype(np.int64) & 0xFFFFFFFF
+            mag = u & 0x7FFFFFFF
+            return np.where(mag > 0x7F800000, 0x7FC00000, np.where(u >> 31 != 0, -mag, mag))
+        if type_ == L.TYPE_DOUBLE:
+            mag = vals & np.int64(0x7FFFFFFFFFFFFFFF)
+            return np.where(mag > 0x7FF0000000000000, 0x7FF8000000000000, np.where(vals < 0, -mag, mag))
+        if type_ == L.TYPE_UINT64:
+            return (vals.view(np.uint64) ^ np.uint64(1 << 63)).view(np.int64)
+        return vals
 
     def _group_cols(self, by):
         cols = [int(by)] if isinstance(by, (int, np.integer)) else [int(c) for c in by]

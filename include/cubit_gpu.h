@@ -874,6 +874,66 @@ int cubit_bitslice_aggregate(cubit_ctx *ctx, const uint64_t *const *d_slices, ui
                              const uint64_t *d_validity, const uint64_t *d_filter, uint64_t n_rows,
                              int type, int64_t base, uint32_t ops, int64_t *d_out);
 
+/* Selection by rank: the k-th smallest / largest value of col, or quantile_disc(col, q), over the
+ * qualifying rows where col is not NULL (the reference's quantile ignores NULLs), ready on the
+ * context's stream with no host round trip. d_out (device, 6 int64) =
+ * {value, found, count_below, count_equal, count_valid, count_rows}: value in the form
+ * cubit_table_column_statistics reports (FLOAT / DOUBLE bit patterns with NaN greatest and -0.0 = +0.0
+ * reported as +0.0, UINT64 bits, a dictionary column's codes), as cubit_table_aggregate's min / max;
+ * found = 0 (and value = count_below = count_equal = 0) when no non-NULL row qualifies or the rank is
+ * at or past count_valid; count_below = the qualifying non-NULL rows strictly before the value in
+ * the direction asked, count_equal = those equal to it; count_valid / count_rows as
+ * cubit_table_aggregate's. An empty partition, or a filter that folds to FALSE, gives six zeros.
+ *   mode: CUBIT_SELECT_RANK (k = the 0-based rank, ascending), CUBIT_SELECT_RANK_DESC (k = 0 is the
+ * largest) or CUBIT_SELECT_QUANTILE: the rank is max(1, n - floor(n - n * q)) - 1 with n =
+ * count_valid, computed on the device in double arithmetic — the reference's Interpolator<true>::Index
+ * for a non-DECIMAL q (src/include/duckdb/core_functions/aggregate/quantile_sort_tree.hpp:166-188);
+ * q outside [0, 1] or NaN is CUBIT_ERR_INVALID. k is ignored with QUANTILE, q otherwise.
+ *   Two paths give the same six numbers, chosen as cubit_table_aggregate chooses (flags below; without
+ * a force flag the path estimated to move fewer bytes). From the slices (a usable bit-sliced index
+ * on col, cubit_table_use_sliced on, no update record of col visible to txn): a radix select over
+ * the slices, most significant first, 4 slices per pass; pass 0 evaluates the filter program
+ * (visibility and zonemap skip included), writes the candidates F AND valid to one scratch bitvector
+ * and histograms the first chunk, each later pass narrows the candidates by the chosen bucket and
+ * histograms the next chunk, and one workgroup after each pass walks the histogram on the device. About
+ * (K [+ 1] + 1 + 2b - 4 + 2 * (passes - 1)) / 8 bytes per row of the evaluated zones. From the column:
+ * scan into scratch, probe with validity (visible MVCC updates applied), then a radix select over
+ * the probed values, 8 bits per pass. cubit_table_last_select tells which ran and its passes (either
+ * pointer may be NULL). Partitions of 2^47 rows or more are refused on the slice path.
+ *   Not offered: several ranks per call; quantile_cont and median (they interpolate between two
+ * ranks, which a caller gets from two RANK calls); a DECIMAL-typed q; anything through the table
+ * function (DuckDB v1.1.2 pushes neither an aggregate nor a LIMIT into seq_scan). */
+#define CUBIT_SELECT_RANK 0      /* k = 0-based rank among the qualifying non-NULL rows, ascending */
+#define CUBIT_SELECT_RANK_DESC 1 /* ... descending: k = 0 is the largest */
+#define CUBIT_SELECT_QUANTILE 2  /* quantile_disc(col, q), 0 <= q <= 1 */
+#define CUBIT_SELECT_DESC_ROWS 1u     /* cubit_table_top_n: ORDER BY col DESC */
+#define CUBIT_SELECT_FROM_SLICES 16u  /* as CUBIT_AGG_FROM_SLICES */
+#define CUBIT_SELECT_FROM_COLUMN 32u  /* as CUBIT_AGG_FROM_COLUMN */
+#define CUBIT_SELECT_NO_ZONEMAP 64u   /* as CUBIT_AGG_NO_ZONEMAP */
+int cubit_table_select(cubit_table *t, const cubit_filter_node *nodes, uint32_t n_nodes, const cubit_txn *txn,
+                       int col, int mode, uint64_t k, double q, uint32_t flags, int64_t *d_out);
+int cubit_table_last_select(cubit_table *t, int *from_slices, uint32_t *n_passes);
+/* The slice path's kernels on a caller's slices: arguments as cubit_bitslice_aggregate's, mode / k / q
+ * and d_out as cubit_table_select's. The candidate bitvector lives in context scratch. */
+int cubit_bitslice_select(cubit_ctx *ctx, const uint64_t *const *d_slices, uint32_t n_slices,
+                          const uint64_t *d_validity, const uint64_t *d_filter, uint64_t n_rows, int type,
+                          int64_t base, int mode, uint64_t k, double q, int64_t *d_out);
+/* ... WHERE <filter> ORDER BY col [DESC], rowid LIMIT k: the global row ids of the first k qualifying
+ * non-NULL rows into d_rowids, in ascending row-id order — every row strictly before the threshold
+ * value (the value of rank k - 1), then the lowest row ids among the rows equal to it until k.
+ * *d_count = min(k, count_valid); d_out as cubit_table_select's for rank k - 1 in the direction asked.
+ * NULL rows are never returned: when fewer than k non-NULL rows qualify, found = 0 and
+ * count_rows - count_valid is what NULLS LAST would append. k = 0 writes no id, *d_count = 0 and six
+ * zeros. capacity < k is CUBIT_ERR_CAPACITY; a VARCHAR or dictionary column is CUBIT_ERR_UNSUPPORTED.
+ * flags: CUBIT_SELECT_DESC_ROWS | the path flags above. The call waits for its result: it reads the
+ * six numbers back and then runs two ordered scans through the planner with the same txn (filter AND
+ * col before the threshold; filter AND col = the threshold), so any column and either select path
+ * works and visible MVCC updates are the planner's; scratch for count_below + count_equal ids is
+ * allocated for the call. */
+int cubit_table_top_n(cubit_table *t, const cubit_filter_node *nodes, uint32_t n_nodes, const cubit_txn *txn, int col,
+                      uint64_t k, uint32_t flags, int64_t *d_rowids, uint64_t capacity, uint64_t *d_count,
+                      int64_t *d_out);
+
 #ifdef __cplusplus
 }
 #endif
