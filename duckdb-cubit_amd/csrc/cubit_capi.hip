@@ -220,6 +220,26 @@ int upload_live(cubit_ctx* ctx, const std::vector<uint32_t>& zones, uint32_t per
     return CUBIT_OK;
 }
 
+// The EvalArgs of a fused kernel that walks tiles of tile_words words and arrives on the context's
+// ticket: the tiles that hold rows, or — live non-empty (zonemap skip) — the live zones' tiles, staged
+// by upload_live. The caller sets `count` when its launcher does not.
+int tile_eval_args(cubit_ctx* ctx, const EvalProgram& prog, uint64_t n_rows, int64_t row_base, uint64_t tile_words,
+                   const std::vector<uint32_t>& live, EvalArgs& a) {
+    a = EvalArgs{};
+    a.prog = prog;
+    a.n_rows = n_rows;
+    a.n_words = (n_rows + 63) / 64;
+    a.row_base = row_base;
+    a.ticket = ctx->ticket;
+    a.num_tiles = (uint32_t)((a.n_words + tile_words - 1) / tile_words);
+    if (!live.empty()) {
+        uint32_t n_live = 0;
+        if (int rc = upload_live(ctx, live, (uint32_t)(kZoneWords / tile_words), &a.live, &n_live)) return rc;
+        a.num_tiles = n_live;
+    }
+    return CUBIT_OK;
+}
+
 enum class RunMode { kDecode, kCount };
 
 // What a decode of one bitvector alone does with the bitvector's row list (cubit_row_list.hpp):
@@ -827,15 +847,13 @@ int cubit_bitslice_aggregate(cubit_ctx* ctx, const uint64_t* const* d_slices, ui
     g.n_slices = n_slices;
     g.validity = d_validity;
     g.workspace = ctx->agg;
-    EvalArgs a{};
+    EvalProgram prog{};
     if (d_filter) {  // a one-leaf program; NULL: the zero-leaf form, every row below n_rows
-        a.prog.leaf[0] = d_filter;
-        a.prog.n_leaves = 1;
+        prog.leaf[0] = d_filter;
+        prog.n_leaves = 1;
     }
-    a.n_rows = n_rows;
-    a.n_words = (n_rows + 63) / 64;
-    a.ticket = ctx->ticket;
-    a.num_tiles = (uint32_t)((a.n_words + kAggTileWords - 1) / kAggTileWords);  // the tiles that hold rows
+    EvalArgs a;
+    if (int rc = tile_eval_args(ctx, prog, n_rows, 0, kAggTileWords, {}, a)) return rc;
     hipEvent_t e0, e1;
     if (int rc = timing_events(ctx, e0, e1)) return rc;
     HIP_CHECK(launch_eval_slice_aggregate(a, g, ops, type, base, ctx->n_cus, d_out, ctx->stream, e0, e1));
@@ -872,15 +890,13 @@ int cubit_bitslice_select(cubit_ctx* ctx, const uint64_t* const* d_slices, uint3
     g.validity = d_validity;
     g.cand = reinterpret_cast<uint64_t*>(ctx->tmp_ids);
     g.workspace = ctx->sel;
-    EvalArgs a{};
+    EvalProgram prog{};
     if (d_filter) {  // a one-leaf program; NULL: the zero-leaf form, every row below n_rows
-        a.prog.leaf[0] = d_filter;
-        a.prog.n_leaves = 1;
+        prog.leaf[0] = d_filter;
+        prog.n_leaves = 1;
     }
-    a.n_rows = n_rows;
-    a.n_words = (n_rows + 63) / 64;
-    a.ticket = ctx->ticket;
-    a.num_tiles = (uint32_t)((a.n_words + kAggTileWords - 1) / kAggTileWords);  // the tiles that hold rows
+    EvalArgs a;
+    if (int rc = tile_eval_args(ctx, prog, n_rows, 0, kAggTileWords, {}, a)) return rc;
     hipEvent_t e0, e1;
     if (int rc = timing_events(ctx, e0, e1)) return rc;
     HIP_CHECK(launch_slice_select(a, g, mode, k, q, type, base, ctx->n_cus, d_out, ctx->stream, nullptr, e0, e1));
@@ -5227,6 +5243,105 @@ extern "C" int cubit_table_scan_tiles(cubit_table* t, const cubit_filter_node* n
 namespace {
 int probe_impl(cubit_table* t, int col, const cubit_txn* txn, const int64_t* d_rowids, const uint64_t* d_count,
                uint64_t max_n, int64_t* d_out, uint64_t* d_valid);
+
+// What cubit_table_aggregate, cubit_table_aggregate_grouped and cubit_table_select share: one plan of
+// a query over a value column, answered from the column's bit slices (a fused evaluate + reduce) or
+// by the plan's decode into scratch, the probe and a reduction of the probed values. Each entry
+// point keeps its argument checks, its output shape, its path rule, its launches and its last_* flags.
+struct SlicePlan {
+    const Column* c = nullptr;   // the value column
+    const Index* sx = nullptr;   // its bit-sliced index; null: the slices cannot answer (not usable)
+    bool force_slices = false, force_column = false;
+    Emitter em;                  // the filter's program
+    std::vector<uint32_t> live;  // the live zones (empty: every zone)
+    uint64_t est_rows = 0;       // the estimated qualifying rows: n_rows unless the path rule is asked
+    uint64_t live_rows = 0;      // the rows of the live zones
+    bool no_rows = false;        // an empty partition, or the filter folded to FALSE: nothing to launch
+    uint32_t bits() const { return sx ? (uint32_t)sx->bvs.size() : 0; }
+    uint64_t elem_bytes() const { return type_is32(c->type) ? 4 : 8; }
+};
+static_assert(kZoneWords == kAggTileWords, "a zone is one tile of the slice kernels");
+
+// the two path flags; both together are refused
+int forced_path(bool from_slices, bool from_column, SlicePlan& p) {
+    p.force_slices = from_slices;
+    p.force_column = from_column;
+    if (from_slices && from_column) return fail(CUBIT_ERR_INVALID, "both paths forced");
+    return CUBIT_OK;
+}
+
+// Binds the value column and, when the slices can answer, its sliced index: the index exists, the
+// table uses sliced indexes, and no update record of a column the slice path reads (`ruling`: the value
+// column, and the group columns of a grouped query) is visible to txn. FROM_SLICES without that is
+// refused.
+int bind_slices(cubit_table* t, const cubit_txn* txn, int col, const Column& c, const int* ruling, uint32_t n_ruling,
+                SlicePlan& p) {
+    if (int rc = set_device(t->ctx)) return rc;
+    t->ctx->last_tiles = 0;  // no row ids reach the caller, so no tile directory
+    p.c = &c;
+    bool visible_updates = false;
+    for (uint32_t i = 0; i < n_ruling; ++i) {
+        auto uit = t->upd.find(ruling[i]);
+        visible_updates |= txn && uit != t->upd.end() && uit->second.any_visible(txn);
+    }
+    auto sit = t->sliced.find(col);
+    if (sit != t->sliced.end() && !sit->second.empty && t->use_sliced && !visible_updates) p.sx = &sit->second;
+    if (p.force_slices && !p.sx)
+        return fail(CUBIT_ERR_INVALID, "column %d has no usable bit-sliced index%s", col,
+                    visible_updates ? " (an update record of a column the query reads is visible to the transaction)" : "");
+    return CUBIT_OK;
+}
+
+// The plan itself: an empty partition resets the last_* counters; else the estimate (only when the
+// path rule will be asked), the program with its live zones, and the zone counters. p.no_rows: the
+// caller writes its zeros and returns.
+int plan_slice_query(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_nodes, const cubit_txn* txn, bool zonemap,
+                     SlicePlan& p) {
+    if (t->n_rows == 0) {
+        t->last_leaves = t->last_passes = 0;
+        t->last_live = t->last_zones = 0;
+        t->last_sliced = 0;
+        p.no_rows = true;
+        return CUBIT_OK;
+    }
+    p.est_rows = t->n_rows;
+    if (p.sx && !p.force_slices && !p.force_column)
+        if (int rc = cubit_table_estimate_rows(t, nodes, n_nodes, &p.est_rows)) return rc;
+    t->last_zones = real_zones(t);
+    t->last_live = 0;
+    if (int rc = plan_program(t, nodes, n_nodes, txn, p.em, &p.no_rows, zonemap ? &p.live : nullptr)) return rc;
+    if (p.no_rows) return CUBIT_OK;  // folded to FALSE (or the zonemaps rule out every zone)
+    t->last_live = p.live.empty() ? t->last_zones : (uint32_t)p.live.size();
+    p.live_rows = std::min<uint64_t>(t->n_rows, (uint64_t)t->last_live * kZoneRows);
+    return CUBIT_OK;
+}
+
+// The column path up to the reduction: the plan's decode into context scratch laid out as the ids,
+// then the values of each of n_probed columns, then their validity words. The caller probes column k
+// into values_of(k) / valid_of(k) and launches its reduction over `count` of `cap` rows.
+struct ColumnScratch {
+    int64_t* ids;
+    uint64_t* count;
+    uint64_t cap, vwords;
+    uint32_t n_probed;
+    int64_t* values_of(uint32_t k) const { return ids + (1 + k) * cap; }
+    uint64_t* valid_of(uint32_t k) const { return reinterpret_cast<uint64_t*>(ids + (1 + n_probed) * cap + k * vwords); }
+};
+int decode_to_scratch(cubit_table* t, const SlicePlan& p, uint32_t n_probed, ColumnScratch& s) {
+    cubit_ctx* ctx = t->ctx;
+    s.cap = t->n_rows;
+    s.vwords = (s.cap + 63) / 64;
+    s.n_probed = n_probed;
+    if (int rc = ensure_tmp(ctx, (1 + n_probed) * s.cap + n_probed * s.vwords)) return rc;
+    s.ids = ctx->tmp_ids;
+    s.count = agg_count_slot(ctx->agg);
+    // (unordered: the decode must not take tmp_ids for an ordering pass)
+    if (int rc = run_eval(ctx, p.em.prog, t->n_rows, t->row_base, s.ids, s.cap, s.count, nullptr, RunMode::kDecode, true,
+                          false, false, p.live.empty() ? nullptr : &p.live, nullptr))
+        return rc;
+    ctx->last_tiles = 0;  // the directory described ids in scratch, not a caller's buffer
+    return CUBIT_OK;
+}
 }  // namespace
 
 extern "C" int cubit_table_sum_product(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_nodes,
@@ -5345,94 +5460,43 @@ extern "C" int cubit_table_aggregate(cubit_table* t, const cubit_filter_node* no
     constexpr uint32_t kOps = CUBIT_AGG_SUM | CUBIT_AGG_MIN | CUBIT_AGG_MAX;
     if (ops & ~(kOps | CUBIT_AGG_FROM_SLICES | CUBIT_AGG_FROM_COLUMN | CUBIT_AGG_NO_ZONEMAP))
         return fail(CUBIT_ERR_INVALID, "ops %u", ops);
-    const bool force_slices = (ops & CUBIT_AGG_FROM_SLICES) != 0, force_column = (ops & CUBIT_AGG_FROM_COLUMN) != 0;
-    if (force_slices && force_column) return fail(CUBIT_ERR_INVALID, "both paths forced");
+    SlicePlan p;
+    if (int rc = forced_path(ops & CUBIT_AGG_FROM_SLICES, ops & CUBIT_AGG_FROM_COLUMN, p)) return rc;
     auto cit = t->cols.find(col);
     if (cit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column %d not registered", col);
     const Column& c = cit->second;
     if ((ops & CUBIT_AGG_SUM) && (type_is_fp(c.type) || c.type == CUBIT_TYPE_VARCHAR || c.dict))
         return fail(CUBIT_ERR_UNSUPPORTED, "SUM of column %d (type %d): its keys are not linear in the value", col,
                     c.type);
-    if (int rc = set_device(t->ctx)) return rc;
+    if (int rc = bind_slices(t, txn, col, c, &col, 1, p)) return rc;
     cubit_ctx* ctx = t->ctx;
-    ctx->last_tiles = 0;  // no row ids reach the caller, so no tile directory
-    auto sit = t->sliced.find(col);
-    auto uit = t->upd.find(col);
-    const bool visible_updates = txn && uit != t->upd.end() && uit->second.any_visible(txn);
-    const bool usable = sit != t->sliced.end() && !sit->second.empty && t->use_sliced && !visible_updates;
-    if (force_slices && !usable)
-        return fail(CUBIT_ERR_INVALID, "column %d has no usable bit-sliced index%s", col,
-                    visible_updates ? " (an update record is visible to the transaction)" : "");
     t->last_agg_slices = false;
-    if (t->n_rows == 0) {  // empty partition: zero counts
-        t->last_leaves = t->last_passes = 0;
-        t->last_live = t->last_zones = 0;
-        t->last_sliced = 0;
+    if (int rc = plan_slice_query(t, nodes, n_nodes, txn, !(ops & CUBIT_AGG_NO_ZONEMAP), p)) return rc;
+    if (p.no_rows) {  // zero counts
         HIP_CHECK(hipMemsetAsync(d_out, 0, 6 * sizeof(int64_t), ctx->stream));
         return CUBIT_OK;
     }
-    uint64_t est_rows = t->n_rows;
-    if (usable && !force_slices && !force_column)
-        if (int rc = cubit_table_estimate_rows(t, nodes, n_nodes, &est_rows)) return rc;
-    Emitter em;
-    bool empty = false;
-    std::vector<uint32_t> live;
-    t->last_zones = real_zones(t);
-    t->last_live = 0;
-    if (int rc = plan_program(t, nodes, n_nodes, txn, em, &empty, (ops & CUBIT_AGG_NO_ZONEMAP) ? nullptr : &live))
-        return rc;
-    if (empty) {  // the filter folded to FALSE (or the zonemaps rule out every zone)
-        HIP_CHECK(hipMemsetAsync(d_out, 0, 6 * sizeof(int64_t), ctx->stream));
-        return CUBIT_OK;
-    }
-    t->last_live = live.empty() ? t->last_zones : (uint32_t)live.size();
-    const uint64_t live_rows = std::min<uint64_t>(t->n_rows, (uint64_t)t->last_live * kZoneRows);
-    const uint32_t bits = usable ? (uint32_t)sit->second.bvs.size() : 0;
-    if (aggregate_from_slices(force_slices, force_column, usable, bits, em.prog.n_leaves, c.validity != nullptr,
-                              live_rows, t->n_rows, est_rows, type_is32(c.type) ? 4 : 8)) {
-        if (t->n_rows >= (1ull << 47))
-            return fail(CUBIT_ERR_INVALID, "%llu rows exceed 2^47", (unsigned long long)t->n_rows);
-        const Index& sx = sit->second;
+    if (aggregate_from_slices(p.force_slices, p.force_column, p.sx != nullptr, p.bits(), p.em.prog.n_leaves,
+                              c.validity != nullptr, p.live_rows, t->n_rows, p.est_rows, p.elem_bytes())) {
         SliceAggArgs g{};
-        g.slices = slice_set(sx);
-        g.n_slices = bits;
+        g.slices = slice_set(*p.sx);
+        g.n_slices = p.bits();
         g.validity = c.validity;
         g.workspace = ctx->agg;
-        EvalArgs a{};
-        a.prog = em.prog;
-        a.n_rows = t->n_rows;
-        a.n_words = (t->n_rows + 63) / 64;
-        a.row_base = t->row_base;
-        a.ticket = ctx->ticket;
-        a.num_tiles = (uint32_t)((a.n_words + kAggTileWords - 1) / kAggTileWords);
-        if (!live.empty()) {  // zonemap skip: a zone is one tile of the kernel
-            static_assert(kZoneWords == kAggTileWords, "a zone is one aggregate tile");
-            uint32_t n_live = 0;
-            if (int rc = upload_live(ctx, live, 1, &a.live, &n_live)) return rc;
-            a.num_tiles = n_live;
-        }
+        EvalArgs a;
+        if (int rc = tile_eval_args(ctx, p.em.prog, t->n_rows, t->row_base, kAggTileWords, p.live, a)) return rc;
         hipEvent_t e0, e1;
         if (int rc = timing_events(ctx, e0, e1)) return rc;
-        HIP_CHECK(launch_eval_slice_aggregate(a, g, ops & kOps, c.type, sx.vmin, ctx->n_cus, d_out, ctx->stream, e0, e1));
+        HIP_CHECK(launch_eval_slice_aggregate(a, g, ops & kOps, c.type, p.sx->vmin, ctx->n_cus, d_out, ctx->stream, e0, e1));
         t->last_agg_slices = true;
         t->last_sliced++;
         return CUBIT_OK;
     }
-    // the column path: ids, probed values and their validity words in context scratch
-    const uint64_t cap = t->n_rows;
-    const uint64_t vwords = (cap + 63) / 64;
-    if (int rc = ensure_tmp(ctx, 2 * cap + vwords)) return rc;
-    int64_t* ids = ctx->tmp_ids;
-    int64_t* xv = ctx->tmp_ids + cap;
-    uint64_t* vw = reinterpret_cast<uint64_t*>(ctx->tmp_ids + 2 * cap);
-    uint64_t* count = agg_count_slot(ctx->agg);
-    // (unordered: the decode must not take tmp_ids for an ordering pass)
-    if (int rc = run_eval(ctx, em.prog, t->n_rows, t->row_base, ids, cap, count, nullptr, RunMode::kDecode, true, false,
-                          false, live.empty() ? nullptr : &live, nullptr))
-        return rc;
-    ctx->last_tiles = 0;  // the directory described ids in scratch, not a caller's buffer
-    if (int rc = probe_impl(t, col, txn, ids, count, cap, xv, vw)) return rc;
-    HIP_CHECK(launch_aggregate_arrays(xv, vw, count, cap, ops & kOps, c.type, ctx->agg, d_out, ctx->stream));
+    ColumnScratch s;
+    if (int rc = decode_to_scratch(t, p, 1, s)) return rc;
+    if (int rc = probe_impl(t, col, txn, s.ids, s.count, s.cap, s.values_of(0), s.valid_of(0))) return rc;
+    HIP_CHECK(launch_aggregate_arrays(s.values_of(0), s.valid_of(0), s.count, s.cap, ops & kOps, c.type, ctx->agg, d_out,
+                                      ctx->stream));
     return CUBIT_OK;
 }
 
@@ -5455,96 +5519,45 @@ extern "C" int cubit_table_select(cubit_table* t, const cubit_filter_node* nodes
     if (mode == CUBIT_SELECT_QUANTILE && !(q >= 0.0 && q <= 1.0)) return fail(CUBIT_ERR_INVALID, "quantile %g outside [0, 1]", q);
     if (flags & ~(CUBIT_SELECT_FROM_SLICES | CUBIT_SELECT_FROM_COLUMN | CUBIT_SELECT_NO_ZONEMAP))
         return fail(CUBIT_ERR_INVALID, "flags %u", flags);
-    const bool force_slices = (flags & CUBIT_SELECT_FROM_SLICES) != 0, force_column = (flags & CUBIT_SELECT_FROM_COLUMN) != 0;
-    if (force_slices && force_column) return fail(CUBIT_ERR_INVALID, "both paths forced");
+    SlicePlan p;
+    if (int rc = forced_path(flags & CUBIT_SELECT_FROM_SLICES, flags & CUBIT_SELECT_FROM_COLUMN, p)) return rc;
     auto cit = t->cols.find(col);
     if (cit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column %d not registered", col);
     const Column& c = cit->second;
-    if (int rc = set_device(t->ctx)) return rc;
+    if (int rc = bind_slices(t, txn, col, c, &col, 1, p)) return rc;
     cubit_ctx* ctx = t->ctx;
-    ctx->last_tiles = 0;  // no row ids reach the caller, so no tile directory
-    auto sit = t->sliced.find(col);
-    auto uit = t->upd.find(col);
-    const bool visible_updates = txn && uit != t->upd.end() && uit->second.any_visible(txn);
-    const bool usable = sit != t->sliced.end() && !sit->second.empty && t->use_sliced && !visible_updates;
-    if (force_slices && !usable)
-        return fail(CUBIT_ERR_INVALID, "column %d has no usable bit-sliced index%s", col,
-                    visible_updates ? " (an update record is visible to the transaction)" : "");
     t->last_sel_slices = false;
     t->last_sel_passes = 0;
-    if (t->n_rows == 0) {  // empty partition: zero counts, found = 0
-        t->last_leaves = t->last_passes = 0;
-        t->last_live = t->last_zones = 0;
-        t->last_sliced = 0;
-        HIP_CHECK(hipMemsetAsync(d_out, 0, 6 * sizeof(int64_t), ctx->stream));
-        return CUBIT_OK;
-    }
-    uint64_t est_rows = t->n_rows;
-    if (usable && !force_slices && !force_column)
-        if (int rc = cubit_table_estimate_rows(t, nodes, n_nodes, &est_rows)) return rc;
-    Emitter em;
-    bool empty = false;
-    std::vector<uint32_t> live;
-    t->last_zones = real_zones(t);
-    t->last_live = 0;
-    if (int rc = plan_program(t, nodes, n_nodes, txn, em, &empty, (flags & CUBIT_SELECT_NO_ZONEMAP) ? nullptr : &live))
-        return rc;
-    if (empty) {  // the filter folded to FALSE (or the zonemaps rule out every zone)
+    if (int rc = plan_slice_query(t, nodes, n_nodes, txn, !(flags & CUBIT_SELECT_NO_ZONEMAP), p)) return rc;
+    if (p.no_rows) {  // zero counts, found = 0
         HIP_CHECK(hipMemsetAsync(d_out, 0, 6 * sizeof(int64_t), ctx->stream));
         return CUBIT_OK;
     }
     if (int rc = ensure_select(ctx)) return rc;
-    t->last_live = live.empty() ? t->last_zones : (uint32_t)live.size();
-    const uint64_t live_rows = std::min<uint64_t>(t->n_rows, (uint64_t)t->last_live * kZoneRows);
-    const uint32_t bits = usable ? (uint32_t)sit->second.bvs.size() : 0;
-    if (select_from_slices(force_slices, force_column, usable, bits, em.prog.n_leaves, c.validity != nullptr, live_rows,
-                           t->n_rows, est_rows, type_is32(c.type) ? 4 : 8)) {
-        if (t->n_rows >= (1ull << 47))
-            return fail(CUBIT_ERR_INVALID, "%llu rows exceed 2^47", (unsigned long long)t->n_rows);
+    if (select_from_slices(p.force_slices, p.force_column, p.sx != nullptr, p.bits(), p.em.prog.n_leaves,
+                           c.validity != nullptr, p.live_rows, t->n_rows, p.est_rows, p.elem_bytes())) {
         if (int rc = ensure_tmp(ctx, padded_words(t->n_rows))) return rc;  // the candidate bitvector
-        const Index& sx = sit->second;
         SliceSelectArgs g{};
-        g.slices = slice_set(sx);
-        g.n_slices = bits;
+        g.slices = slice_set(*p.sx);
+        g.n_slices = p.bits();
         g.validity = c.validity;
         g.cand = reinterpret_cast<uint64_t*>(ctx->tmp_ids);
         g.workspace = ctx->sel;
-        EvalArgs a{};
-        a.prog = em.prog;
-        a.n_rows = t->n_rows;
-        a.n_words = (t->n_rows + 63) / 64;
-        a.row_base = t->row_base;
-        a.ticket = ctx->ticket;
-        a.num_tiles = (uint32_t)((a.n_words + kAggTileWords - 1) / kAggTileWords);
-        if (!live.empty()) {  // zonemap skip: a zone is one tile of the kernels
-            uint32_t n_live = 0;
-            if (int rc = upload_live(ctx, live, 1, &a.live, &n_live)) return rc;
-            a.num_tiles = n_live;
-        }
+        EvalArgs a;
+        if (int rc = tile_eval_args(ctx, p.em.prog, t->n_rows, t->row_base, kAggTileWords, p.live, a)) return rc;
         hipEvent_t e0, e1;
         if (int rc = timing_events(ctx, e0, e1)) return rc;
-        HIP_CHECK(launch_slice_select(a, g, mode, k, q, c.type, sx.vmin, ctx->n_cus, d_out, ctx->stream,
+        HIP_CHECK(launch_slice_select(a, g, mode, k, q, c.type, p.sx->vmin, ctx->n_cus, d_out, ctx->stream,
                                       &t->last_sel_passes, e0, e1));
         t->last_sel_slices = true;
         t->last_sliced++;
         return CUBIT_OK;
     }
-    // the column path: ids, probed values and their validity words in context scratch
-    const uint64_t cap = t->n_rows;
-    const uint64_t vwords = (cap + 63) / 64;
-    if (int rc = ensure_tmp(ctx, 2 * cap + vwords)) return rc;
-    int64_t* ids = ctx->tmp_ids;
-    int64_t* xv = ctx->tmp_ids + cap;
-    uint64_t* vw = reinterpret_cast<uint64_t*>(ctx->tmp_ids + 2 * cap);
-    uint64_t* count = agg_count_slot(ctx->agg);
-    // (unordered: the decode must not take tmp_ids for an ordering pass)
-    if (int rc = run_eval(ctx, em.prog, t->n_rows, t->row_base, ids, cap, count, nullptr, RunMode::kDecode, true, false,
-                          false, live.empty() ? nullptr : &live, nullptr))
-        return rc;
-    ctx->last_tiles = 0;  // the directory described ids in scratch, not a caller's buffer
-    if (int rc = probe_impl(t, col, txn, ids, count, cap, xv, vw)) return rc;
-    HIP_CHECK(launch_select_arrays(xv, vw, count, cap, mode, k, q, c.type, ctx->sel, d_out, ctx->stream,
-                                   &t->last_sel_passes));
+    ColumnScratch s;
+    if (int rc = decode_to_scratch(t, p, 1, s)) return rc;
+    if (int rc = probe_impl(t, col, txn, s.ids, s.count, s.cap, s.values_of(0), s.valid_of(0))) return rc;
+    HIP_CHECK(launch_select_arrays(s.values_of(0), s.valid_of(0), s.count, s.cap, mode, k, q, c.type, ctx->sel, d_out,
+                                   ctx->stream, &t->last_sel_passes));
     return CUBIT_OK;
 }
 
@@ -5729,8 +5742,8 @@ extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_
     constexpr uint32_t kOps = CUBIT_AGG_SUM | CUBIT_AGG_MIN | CUBIT_AGG_MAX;
     if (ops & ~(kOps | CUBIT_AGG_FROM_SLICES | CUBIT_AGG_FROM_COLUMN | CUBIT_AGG_NO_ZONEMAP))
         return fail(CUBIT_ERR_INVALID, "ops %u", ops);
-    const bool force_slices = (ops & CUBIT_AGG_FROM_SLICES) != 0, force_column = (ops & CUBIT_AGG_FROM_COLUMN) != 0;
-    if (force_slices && force_column) return fail(CUBIT_ERR_INVALID, "both paths forced");
+    SlicePlan p;
+    if (int rc = forced_path(ops & CUBIT_AGG_FROM_SLICES, ops & CUBIT_AGG_FROM_COLUMN, p)) return rc;
     auto cit = t->cols.find(col);
     if (cit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column %d not registered", col);
     const Column& c = cit->second;
@@ -5742,46 +5755,19 @@ extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_
     if (int rc = group_columns(t, group_cols, n_group_cols, gc, &n1, &n2)) return rc;
     const uint32_t n_groups = n1 * n2;
     if (cap_groups < n_groups) return fail(CUBIT_ERR_CAPACITY, "%u groups, room for %u", n_groups, cap_groups);
-    if (int rc = set_device(t->ctx)) return rc;
+    // an update record of the value column or of a group column rules the slices out
+    int ruling[1 + CUBIT_AGG_MAX_GROUP_COLS] = {col};
+    for (uint32_t k = 0; k < n_group_cols; ++k) ruling[1 + k] = gc[k].col;
+    if (int rc = bind_slices(t, txn, col, c, ruling, 1 + n_group_cols, p)) return rc;
     cubit_ctx* ctx = t->ctx;
-    ctx->last_tiles = 0;  // no row ids reach the caller, so no tile directory
-    auto sit = t->sliced.find(col);
-    auto visible = [&](int column) {
-        auto uit = t->upd.find(column);
-        return txn && uit != t->upd.end() && uit->second.any_visible(txn);
-    };
-    bool visible_updates = visible(col);
-    for (uint32_t k = 0; k < n_group_cols; ++k) visible_updates |= visible(gc[k].col);
-    const bool usable = sit != t->sliced.end() && !sit->second.empty && t->use_sliced && !visible_updates;
-    if (force_slices && !usable)
-        return fail(CUBIT_ERR_INVALID, "column %d has no usable bit-sliced index%s", col,
-                    visible_updates ? " (an update record of it or of a group column is visible to the transaction)" : "");
     t->last_grouped_slices = false;
     t->last_grouped_groups = n_groups;
     t->last_grouped_launches = 0;
     if (n_groups == 0) return CUBIT_OK;
     // every group starts as six zeros: the kernels write the groups that reach them
     HIP_CHECK(hipMemsetAsync(d_out, 0, (size_t)n_groups * 6 * sizeof(int64_t), ctx->stream));
-    if (t->n_rows == 0) {  // empty partition
-        t->last_leaves = t->last_passes = 0;
-        t->last_live = t->last_zones = 0;
-        t->last_sliced = 0;
-        return CUBIT_OK;
-    }
-    uint64_t est_rows = t->n_rows;
-    if (usable && !force_slices && !force_column)
-        if (int rc = cubit_table_estimate_rows(t, nodes, n_nodes, &est_rows)) return rc;
-    Emitter em;
-    bool empty = false;
-    std::vector<uint32_t> live;
-    t->last_zones = real_zones(t);
-    t->last_live = 0;
-    if (int rc = plan_program(t, nodes, n_nodes, txn, em, &empty, (ops & CUBIT_AGG_NO_ZONEMAP) ? nullptr : &live))
-        return rc;
-    if (empty) return CUBIT_OK;  // the filter folded to FALSE (or the zonemaps rule out every zone)
-    t->last_live = live.empty() ? t->last_zones : (uint32_t)live.size();
-    const uint64_t live_rows = std::min<uint64_t>(t->n_rows, (uint64_t)t->last_live * kZoneRows);
-    const uint32_t bits = usable ? (uint32_t)sit->second.bvs.size() : 0;
+    if (int rc = plan_slice_query(t, nodes, n_nodes, txn, !(ops & CUBIT_AGG_NO_ZONEMAP), p)) return rc;
+    if (p.no_rows) return CUBIT_OK;
     if (int rc = ensure_grouped(ctx)) return rc;
 
     // the slots that have a bitvector: a key's index leaf, and the NULL slot of a nullable column
@@ -5794,33 +5780,22 @@ extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_
     }
     const bool two = n_group_cols > 1;
     const bool minmax = (ops & (CUBIT_AGG_MIN | CUBIT_AGG_MAX)) != 0;
-    const uint32_t row_bits = bits + em.prog.n_leaves + (c.validity ? 1u : 0u);
+    const uint32_t row_bits = p.bits() + p.em.prog.n_leaves + (c.validity ? 1u : 0u);
     bool swapped = false;
     const std::vector<GroupBatch> batches =
         split_group_batches((uint32_t)leaves[0].size(), two ? (uint32_t)leaves[1].size() : 0u, two,
                             minmax ? kGroupBatchMinMax : kGroupBatchSum, row_bits, &swapped);
-    uint64_t elem_bytes[1 + CUBIT_AGG_MAX_GROUP_COLS] = {type_is32(c.type) ? 4u : 8u, 0, 0};
+    uint64_t elem_bytes[1 + CUBIT_AGG_MAX_GROUP_COLS] = {p.elem_bytes(), 0, 0};
     for (uint32_t k = 0; k < n_group_cols; ++k) elem_bytes[1 + k] = type_is32(gc[k].c->type) ? 4 : 8;
-    if (grouped_from_slices(force_slices, force_column, usable, batches.empty() ? row_bits : group_batches_bits(batches, row_bits),
-                            em.prog.n_leaves, live_rows, t->n_rows, est_rows, elem_bytes, 1 + n_group_cols)) {
-        if (t->n_rows >= (1ull << 47))
-            return fail(CUBIT_ERR_INVALID, "%llu rows exceed 2^47", (unsigned long long)t->n_rows);
-        const Index& sx = sit->second;
+    if (grouped_from_slices(p.force_slices, p.force_column, p.sx != nullptr,
+                            batches.empty() ? row_bits : group_batches_bits(batches, row_bits), p.em.prog.n_leaves,
+                            p.live_rows, t->n_rows, p.est_rows, elem_bytes, 1 + n_group_cols)) {
         SliceAggArgs g{};
-        g.slices = slice_set(sx);
-        g.n_slices = bits;
+        g.slices = slice_set(*p.sx);
+        g.n_slices = p.bits();
         g.validity = c.validity;
-        EvalArgs a{};
-        a.prog = em.prog;
-        a.n_rows = t->n_rows;
-        a.n_words = (t->n_rows + 63) / 64;
-        a.row_base = t->row_base;
-        a.num_tiles = (uint32_t)((a.n_words + kAggTileWords - 1) / kAggTileWords);
-        if (!live.empty()) {  // zonemap skip: a zone is one tile of the kernel
-            uint32_t n_live = 0;
-            if (int rc = upload_live(ctx, live, 1, &a.live, &n_live)) return rc;
-            a.num_tiles = n_live;
-        }
+        EvalArgs a;  // (the kernel counts each group's rows in its partials and takes no ticket)
+        if (int rc = tile_eval_args(ctx, p.em.prog, t->n_rows, t->row_base, kAggTileWords, p.live, a)) return rc;
         const std::vector<GroupLeaf>& la = leaves[swapped ? 1 : 0];
         const std::vector<GroupLeaf>& lb = leaves[swapped ? 0 : 1];
         for (const GroupBatch& b : batches) {
@@ -5849,7 +5824,7 @@ extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_
             }
             hipEvent_t e0, e1;
             if (int rc = timing_events(ctx, e0, e1)) return rc;
-            HIP_CHECK(launch_eval_slice_aggregate_grouped(a, g, q, ops & kOps, c.type, sx.vmin, ctx->n_cus, d_out,
+            HIP_CHECK(launch_eval_slice_aggregate_grouped(a, g, q, ops & kOps, c.type, p.sx->vmin, ctx->n_cus, d_out,
                                                           ctx->stream, e0, e1));
             t->last_grouped_launches++;
         }
@@ -5857,22 +5832,10 @@ extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_
         t->last_sliced++;
         return CUBIT_OK;
     }
-    // the column path: ids, then per probed column (the value column, the group columns) its values,
-    // then their validity words, in context scratch
-    const uint64_t cap = t->n_rows;
-    const uint64_t vwords = (cap + 63) / 64;
-    const uint32_t n_probed = 1 + n_group_cols;
-    if (int rc = ensure_tmp(ctx, (1 + n_probed) * cap + n_probed * vwords)) return rc;
-    int64_t* ids = ctx->tmp_ids;
-    auto values_of = [&](uint32_t k) { return ctx->tmp_ids + (1 + k) * cap; };
-    auto valid_of = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(ctx->tmp_ids + (1 + n_probed) * cap + k * vwords); };
-    uint64_t* count = agg_count_slot(ctx->agg);
-    // (unordered: the decode must not take tmp_ids for an ordering pass)
-    if (int rc = run_eval(ctx, em.prog, t->n_rows, t->row_base, ids, cap, count, nullptr, RunMode::kDecode, true, false,
-                          false, live.empty() ? nullptr : &live, nullptr))
-        return rc;
-    ctx->last_tiles = 0;  // the directory described ids in scratch, not a caller's buffer
-    if (int rc = probe_impl(t, col, txn, ids, count, cap, values_of(0), valid_of(0))) return rc;
+    // the column path: the value column and the group columns are probed
+    ColumnScratch cs;
+    if (int rc = decode_to_scratch(t, p, 1 + n_group_cols, cs)) return rc;
+    if (int rc = probe_impl(t, col, txn, cs.ids, cs.count, cs.cap, cs.values_of(0), cs.valid_of(0))) return rc;
     GroupColArgs ga{};
     ga.n_cols = n_group_cols;
     ga.n2 = n2;
@@ -5881,11 +5844,12 @@ extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_
         ctx->gkeys_pending = false;
     }
     for (uint32_t k = 0; k < n_group_cols; ++k) {
-        if (int rc = probe_impl(t, gc[k].col, txn, ids, count, cap, values_of(1 + k), valid_of(1 + k))) return rc;
+        if (int rc = probe_impl(t, gc[k].col, txn, cs.ids, cs.count, cs.cap, cs.values_of(1 + k), cs.valid_of(1 + k)))
+            return rc;
         const GroupSlots& s = gc[k].slots;
         std::copy(s.keys.begin(), s.keys.end(), ctx->gkeys_host + (size_t)k * CUBIT_AGG_MAX_GROUPS);
-        ga.v[k] = values_of(1 + k);
-        ga.valid[k] = valid_of(1 + k);
+        ga.v[k] = cs.values_of(1 + k);
+        ga.valid[k] = cs.valid_of(1 + k);
         ga.keys[k] = ctx->gkeys_dev + (size_t)k * CUBIT_AGG_MAX_GROUPS;
         ga.n_keys[k] = (uint32_t)s.keys.size();
         ga.null_slot[k] = s.has_null ? (int32_t)s.keys.size() : -1;
@@ -5896,8 +5860,8 @@ extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_
                              hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(hipEventRecord(ctx->gkeys_ev, ctx->stream));
     ctx->gkeys_pending = true;
-    HIP_CHECK(launch_aggregate_arrays_grouped(values_of(0), valid_of(0), ga, n_groups, count, cap, ops & kOps, c.type,
-                                              ctx->gagg, d_out, ctx->stream));
+    HIP_CHECK(launch_aggregate_arrays_grouped(cs.values_of(0), cs.valid_of(0), ga, n_groups, cs.count, cs.cap, ops & kOps,
+                                              c.type, ctx->gagg, d_out, ctx->stream));
     return CUBIT_OK;
 }
 

@@ -2255,6 +2255,113 @@ __global__ __launch_bounds__(256) void bitslice_compare_kernel(SliceSet sl, uint
     }
 }
 
+// ---- what the kernels that answer a query from the slices share (eval_slice_aggregate,
+// eval_slice_select, eval_slice_aggregate_grouped and the reductions beside them)
+
+// The tile prologue: r = the program over the thread's NW words of the tile (K = 0: every row), cut at
+// n_rows. (The decode and sum kernels pipeline load_tile across tiles and keep their own.)
+template <int K, int FORM, int NW, int THREADS>
+__device__ __forceinline__ void eval_tile(const EvalArgs& a, uint64_t tile_word0, int t, uint64_t (&r)[NW]) {
+    if constexpr (K > 0) {
+        u64x2 v[K][NW / 2];
+        load_tile<K, NW / 2, THREADS>(a, tile_word0, t, v);
+        eval_words<K, NW, FORM>(a.prog, v, r);
+    } else {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) r[j] = ~0ull;
+    }
+    tail_mask<NW, THREADS>(a, tile_word0, t, r);
+}
+
+// Pair p of the thread's words of a bitvector that is not a program leaf (a validity, a group leaf),
+// complemented when neg. whole (uniform): the tile lies below the last word; the tile that holds the
+// last word reads nothing at or past n_words (a caller's bitvector need not be padded).
+template <int THREADS>
+__device__ __forceinline__ u64x2 load_pair(const uint64_t* bv, bool neg, bool whole, uint64_t tile_word0, int p, int t,
+                                           uint64_t n_words) {
+    u64x2 e;
+    if (whole) {
+        e = reinterpret_cast<const u64x2*>(bv + tile_word0)[p * THREADS + t];
+    } else {
+        const uint64_t gw = word_index<THREADS>(tile_word0, 2 * p, t);
+        e.x = gw < n_words ? bv[gw] : 0ull;
+        e.y = gw + 1 < n_words ? bv[gw + 1] : 0ull;
+    }
+    return neg ? ~e : e;
+}
+
+// The partial aggregate a thread, a wave, a workgroup and the finishing wave carry: the 128-bit sum,
+// the least and greatest offset, the valid rows and (ROWS) the rows. Exact integer adds and unsigned
+// min / max, so any order of merges gives the same. In memory it is kSlots words in that order (the
+// ungrouped workspace keeps the first kAggPartial and counts the rows through the ticket).
+template <bool ROWS>
+struct AggPartial {
+    static constexpr int kSlots = ROWS ? 6 : 5;
+    U128 sum{0, 0};
+    uint64_t mn = ~0ull, mx = 0, valid = 0, rows = 0;
+    __device__ __forceinline__ void merge(const AggPartial& o) {
+        sum = u128_add(sum, o.sum);
+        mn = o.mn < mn ? o.mn : mn;
+        mx = o.mx > mx ? o.mx : mx;
+        valid += o.valid;
+        if (ROWS) rows += o.rows;
+    }
+    // butterfly: every lane ends with the wave's partial
+    __device__ __forceinline__ void wave_reduce() {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            AggPartial o;
+            o.sum.lo = __shfl_xor(sum.lo, d, 64);
+            o.sum.hi = __shfl_xor(sum.hi, d, 64);
+            o.mn = __shfl_xor(mn, d, 64);
+            o.mx = __shfl_xor(mx, d, 64);
+            o.valid = __shfl_xor(valid, d, 64);
+            if (ROWS) o.rows = __shfl_xor(rows, d, 64);
+            merge(o);
+        }
+    }
+    template <typename W>
+    __device__ __forceinline__ void store(W* s, int slots = kSlots) const {
+        s[0] = (W)sum.lo;
+        s[1] = (W)sum.hi;
+        s[2] = (W)mn;
+        s[3] = (W)mx;
+        s[4] = (W)valid;
+        if (ROWS && slots > 5) s[5] = (W)rows;
+    }
+    template <typename W>
+    __device__ __forceinline__ static AggPartial load(const W* s) {
+        AggPartial r;
+        r.sum = U128{(uint64_t)s[0], (uint64_t)s[1]};
+        r.mn = (uint64_t)s[2];
+        r.mx = (uint64_t)s[3];
+        r.valid = (uint64_t)s[4];
+        if (ROWS) r.rows = (uint64_t)s[5];
+        return r;
+    }
+    // the per-wave LDS fold: after each wave's lane 0 stored its partial at s + wave·stride and a
+    // barrier, the sum over the n waves
+    __device__ __forceinline__ static AggPartial fold(const uint64_t* s, int n, int stride) {
+        AggPartial r;
+        for (int w = 0; w < n; ++w) r.merge(load(s + w * stride));
+        return r;
+    }
+    // The four result values {sum lo, sum hi, min, max} of the finishing wave. from_slices: the sum
+    // is Σ 2^s·c_s and the offsets count from `base` (slice_agg_combine); else the sum is the values'
+    // and the offsets count from INT64_MIN.
+    __device__ __forceinline__ void result(uint32_t ops, int type, int64_t base, int from_slices, int64_t r[4]) const {
+        if (from_slices) {
+            slice_agg_combine(type, base, valid, sum, mn, mx, ops, r);
+        } else {
+            slice_agg_combine(type, INT64_MIN, valid, U128{0, 0}, mn, mx, ops & ~kAggSum, r);
+            if (ops & kAggSum) {
+                r[0] = (int64_t)sum.lo;
+                r[1] = (int64_t)sum.hi;
+            }
+        }
+    }
+};
+
 // Aggregate: SUM / MIN / MAX / COUNT of the column over the rows a program keeps, from the slices
 // alone (O'Neil & Quass 1997 §3; Rinfret et al. 2001). Fused evaluate + aggregate in the eval_*
 // family: persistent workgroups walk tiles of one zone (load_tile / eval_words / tail_mask, live-tile
@@ -2305,23 +2412,14 @@ __global__ __launch_bounds__(512, 4) void eval_slice_aggregate(EvalArgs a, Slice
     constexpr uint64_t TILE_WORDS = (uint64_t)THREADS * NW;
     static_assert(TILE_WORDS == kAggTileWords, "a tile is one zone");
     constexpr int NWAVES = THREADS / 64;
+    using Partial = AggPartial<true>;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    uint64_t c_rows = 0, c_valid = 0;
-    U128 acc{0, 0};
-    uint64_t mn = ~0ull, mx = 0;
+    Partial part;
     const uint32_t n_idx = a.num_tiles;
     for (uint32_t i = blockIdx.x; i < n_idx; i += gridDim.x) {
         const uint64_t tile_word0 = (uint64_t)tile_at(a, i) * TILE_WORDS;
         uint64_t r[NW];
-        if constexpr (K > 0) {
-            u64x2 v[K][PAIRS];
-            load_tile<K, PAIRS, THREADS>(a, tile_word0, t, v);
-            eval_words<K, NW, FORM>(a.prog, v, r);
-        } else {
-#pragma unroll
-            for (int j = 0; j < NW; ++j) r[j] = ~0ull;
-        }
-        tail_mask<NW, THREADS>(a, tile_word0, t, r);
+        eval_tile<K, FORM, NW, THREADS>(a, tile_word0, t, r);
         u64x2 fv[PAIRS];
 #pragma unroll
         for (int p = 0; p < PAIRS; ++p) {
@@ -2329,23 +2427,14 @@ __global__ __launch_bounds__(512, 4) void eval_slice_aggregate(EvalArgs a, Slice
             fv[p].y = r[2 * p + 1];
         }
         if (g.validity) {
-            if (tile_word0 + TILE_WORDS <= a.n_words) {  // uniform: the whole tile lies below the last word
+            const bool whole = tile_word0 + TILE_WORDS <= a.n_words;
 #pragma unroll
-                for (int p = 0; p < PAIRS; ++p)
-                    fv[p] &= reinterpret_cast<const u64x2*>(g.validity + tile_word0)[p * THREADS + t];
-            } else {  // the tile holding the last word: nothing at or past n_words is read
-#pragma unroll
-                for (int p = 0; p < PAIRS; ++p) {
-                    const uint64_t gw = word_index<THREADS>(tile_word0, 2 * p, t);
-                    fv[p].x &= gw < a.n_words ? g.validity[gw] : 0ull;
-                    fv[p].y &= gw + 1 < a.n_words ? g.validity[gw + 1] : 0ull;
-                }
-            }
+            for (int p = 0; p < PAIRS; ++p) fv[p] &= load_pair<THREADS>(g.validity, false, whole, tile_word0, p, t, a.n_words);
         }
 #pragma unroll
         for (int p = 0; p < PAIRS; ++p) {
-            c_rows += (uint64_t)(__popcll(r[2 * p]) + __popcll(r[2 * p + 1]));
-            c_valid += (uint64_t)(__popcll(fv[p].x) + __popcll(fv[p].y));
+            part.rows += (uint64_t)(__popcll(r[2 * p]) + __popcll(r[2 * p + 1]));
+            part.valid += (uint64_t)(__popcll(fv[p].x) + __popcll(fv[p].y));
         }
         if (!SUM && !MINMAX) continue;
 #pragma unroll
@@ -2356,66 +2445,35 @@ __global__ __launch_bounds__(512, 4) void eval_slice_aggregate(EvalArgs a, Slice
             u64x2 cmin = f, cmax = f, omin = {0ull, 0ull}, omax = {0ull, 0ull};
             int top = (int)g.n_slices - 1;
             switch (g.n_slices & 7u) {  // the top slices that fill no chunk of 8, then whole chunks
-            case 1: agg_chunk<SUM, MINMAX, 1>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
-            case 2: agg_chunk<SUM, MINMAX, 2>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
-            case 3: agg_chunk<SUM, MINMAX, 3>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
-            case 4: agg_chunk<SUM, MINMAX, 4>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
-            case 5: agg_chunk<SUM, MINMAX, 5>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
-            case 6: agg_chunk<SUM, MINMAX, 6>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
-            case 7: agg_chunk<SUM, MINMAX, 7>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax); break;
+            case 1: agg_chunk<SUM, MINMAX, 1>(g.slices, top, pi, f, part.sum, cmin, cmax, omin, omax); break;
+            case 2: agg_chunk<SUM, MINMAX, 2>(g.slices, top, pi, f, part.sum, cmin, cmax, omin, omax); break;
+            case 3: agg_chunk<SUM, MINMAX, 3>(g.slices, top, pi, f, part.sum, cmin, cmax, omin, omax); break;
+            case 4: agg_chunk<SUM, MINMAX, 4>(g.slices, top, pi, f, part.sum, cmin, cmax, omin, omax); break;
+            case 5: agg_chunk<SUM, MINMAX, 5>(g.slices, top, pi, f, part.sum, cmin, cmax, omin, omax); break;
+            case 6: agg_chunk<SUM, MINMAX, 6>(g.slices, top, pi, f, part.sum, cmin, cmax, omin, omax); break;
+            case 7: agg_chunk<SUM, MINMAX, 7>(g.slices, top, pi, f, part.sum, cmin, cmax, omin, omax); break;
             default: break;
             }
             top -= (int)(g.n_slices & 7u);
-            for (; top >= 7; top -= 8) agg_chunk<SUM, MINMAX, 8>(g.slices, top, pi, f, acc, cmin, cmax, omin, omax);
+            for (; top >= 7; top -= 8) agg_chunk<SUM, MINMAX, 8>(g.slices, top, pi, f, part.sum, cmin, cmax, omin, omax);
             if (MINMAX) {
                 // (a word of the pair without a qualifying row gives 2^b - 1 / 0: never below / above
                 // the other word's offset)
                 const uint64_t lo = omin.x < omin.y ? omin.x : omin.y, hi = omax.x > omax.y ? omax.x : omax.y;
-                mn = lo < mn ? lo : mn;
-                mx = hi > mx ? hi : mx;
+                part.mn = lo < part.mn ? lo : part.mn;
+                part.mx = hi > part.mx ? hi : part.mx;
             }
         }
     }
-    // wave, then workgroup: exact integer adds and unsigned min / max, so any order gives the same
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        U128 o;
-        o.lo = __shfl_xor(acc.lo, d, 64);
-        o.hi = __shfl_xor(acc.hi, d, 64);
-        acc = u128_add(acc, o);
-        const uint64_t omn = __shfl_xor(mn, d, 64), omx = __shfl_xor(mx, d, 64);
-        mn = omn < mn ? omn : mn;
-        mx = omx > mx ? omx : mx;
-        c_rows += __shfl_xor(c_rows, d, 64);
-        c_valid += __shfl_xor(c_valid, d, 64);
-    }
-    __shared__ uint64_t s_part[NWAVES][6];
-    if (lane == 0) {
-        s_part[wave][0] = acc.lo;
-        s_part[wave][1] = acc.hi;
-        s_part[wave][2] = mn;
-        s_part[wave][3] = mx;
-        s_part[wave][4] = c_valid;
-        s_part[wave][5] = c_rows;
-    }
+    // wave, then workgroup
+    part.wave_reduce();
+    __shared__ uint64_t s_part[NWAVES][Partial::kSlots];
+    if (lane == 0) part.store(s_part[wave]);
     __syncthreads();
     if (t == 0) {
-        U128 s{0, 0};
-        uint64_t lo = ~0ull, hi = 0, cv = 0, cr = 0;
-        for (int w = 0; w < NWAVES; ++w) {
-            s = u128_add(s, U128{s_part[w][0], s_part[w][1]});
-            lo = s_part[w][2] < lo ? s_part[w][2] : lo;
-            hi = s_part[w][3] > hi ? s_part[w][3] : hi;
-            cv += s_part[w][4];
-            cr += s_part[w][5];
-        }
-        int64_t* part = g.workspace + (uint64_t)kAggPartial * blockIdx.x;
-        part[0] = (int64_t)s.lo;
-        part[1] = (int64_t)s.hi;
-        part[2] = (int64_t)lo;
-        part[3] = (int64_t)hi;
-        part[4] = (int64_t)cv;
-        finish_ticket(a.ticket, a.count, cr);
+        const Partial s = Partial::fold(&s_part[0][0], NWAVES, Partial::kSlots);
+        s.store(g.workspace + (uint64_t)kAggPartial * blockIdx.x, kAggPartial);
+        finish_ticket(a.ticket, a.count, s.rows);
     }
 }
 
@@ -2430,102 +2488,47 @@ __global__ __launch_bounds__(256) void aggregate_arrays_kernel(const int64_t* __
                                                                uint32_t ops, int type, int64_t* __restrict__ workspace) {
     const uint64_t n = min(*d_count, max_n);
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    U128 acc{0, 0};
-    uint64_t mn = ~0ull, mx = 0, cv = 0;
+    using Partial = AggPartial<false>;
+    Partial part;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         if (valid && !((valid[i >> 6] >> (i & 63)) & 1ull)) continue;
         const int64_t v = x[i];
-        ++cv;
-        if (ops & kAggSum) acc = u128_add(acc, U128{(uint64_t)v, type == kTypeUInt64 || v >= 0 ? 0ull : ~0ull});
+        ++part.valid;
+        if (ops & kAggSum) part.sum = u128_add(part.sum, U128{(uint64_t)v, type == kTypeUInt64 || v >= 0 ? 0ull : ~0ull});
         const uint64_t off = (uint64_t)value_key(type, v) ^ 0x8000000000000000ull;
-        mn = off < mn ? off : mn;
-        mx = off > mx ? off : mx;
+        part.mn = off < part.mn ? off : part.mn;
+        part.mx = off > part.mx ? off : part.mx;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        U128 o;
-        o.lo = __shfl_xor(acc.lo, d, 64);
-        o.hi = __shfl_xor(acc.hi, d, 64);
-        acc = u128_add(acc, o);
-        const uint64_t omn = __shfl_xor(mn, d, 64), omx = __shfl_xor(mx, d, 64);
-        mn = omn < mn ? omn : mn;
-        mx = omx > mx ? omx : mx;
-        cv += __shfl_xor(cv, d, 64);
-    }
-    __shared__ uint64_t s_part[4][5];
+    part.wave_reduce();
+    __shared__ uint64_t s_part[4][Partial::kSlots];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_part[wave][0] = acc.lo;
-        s_part[wave][1] = acc.hi;
-        s_part[wave][2] = mn;
-        s_part[wave][3] = mx;
-        s_part[wave][4] = cv;
-    }
+    if (lane == 0) part.store(s_part[wave]);
     __syncthreads();
     if (threadIdx.x == 0) {
-        U128 s{0, 0};
-        uint64_t lo = ~0ull, hi = 0, c = 0;
-        for (int w = 0; w < 4; ++w) {
-            s = u128_add(s, U128{s_part[w][0], s_part[w][1]});
-            lo = s_part[w][2] < lo ? s_part[w][2] : lo;
-            hi = s_part[w][3] > hi ? s_part[w][3] : hi;
-            c += s_part[w][4];
-        }
-        int64_t* part = workspace + (uint64_t)kAggPartial * blockIdx.x;
-        part[0] = (int64_t)s.lo;
-        part[1] = (int64_t)s.hi;
-        part[2] = (int64_t)lo;
-        part[3] = (int64_t)hi;
-        part[4] = (int64_t)c;
+        Partial::fold(&s_part[0][0], 4, Partial::kSlots).store(workspace + (uint64_t)kAggPartial * blockIdx.x);
         // count_rows for the finishing wave (a scan that counted into the slot itself left it there)
         if (blockIdx.x == 0 && d_count != agg_count_slot(workspace)) *agg_count_slot(workspace) = n;
     }
 }
 
 // One wave combines the workgroups' partials (beside sum_partials_kernel: a strided share per lane,
-// then a butterfly) and writes the six result slots. from_slices: the partial sums are Σ 2^s·c_s and
-// the offsets count from `base` (slice_agg_combine); else the sums are the values' and the offsets
-// count from INT64_MIN.
+// then a butterfly) and writes the six result slots (AggPartial::result has from_slices).
 __global__ __launch_bounds__(64) void aggregate_finish_kernel(const int64_t* __restrict__ workspace, int nblocks,
                                                               uint32_t ops, int type, int64_t base, int from_slices,
                                                               int64_t* __restrict__ out) {
     const int lane = threadIdx.x;
-    U128 acc{0, 0};
-    uint64_t mn = ~0ull, mx = 0, cv = 0;
-    for (int b = lane; b < nblocks; b += 64) {
-        const int64_t* part = workspace + (uint64_t)kAggPartial * b;
-        acc = u128_add(acc, U128{(uint64_t)part[0], (uint64_t)part[1]});
-        mn = (uint64_t)part[2] < mn ? (uint64_t)part[2] : mn;
-        mx = (uint64_t)part[3] > mx ? (uint64_t)part[3] : mx;
-        cv += (uint64_t)part[4];
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        U128 o;
-        o.lo = __shfl_xor(acc.lo, d, 64);
-        o.hi = __shfl_xor(acc.hi, d, 64);
-        acc = u128_add(acc, o);
-        const uint64_t omn = __shfl_xor(mn, d, 64), omx = __shfl_xor(mx, d, 64);
-        mn = omn < mn ? omn : mn;
-        mx = omx > mx ? omx : mx;
-        cv += __shfl_xor(cv, d, 64);
-    }
+    using Partial = AggPartial<false>;
+    Partial part;
+    for (int b = lane; b < nblocks; b += 64) part.merge(Partial::load(workspace + (uint64_t)kAggPartial * b));
+    part.wave_reduce();
     if (lane == 0) {
         int64_t r[4];
-        if (from_slices) {
-            slice_agg_combine(type, base, cv, acc, mn, mx, ops, r);
-        } else {
-            slice_agg_combine(type, INT64_MIN, cv, U128{0, 0}, mn, mx, ops & ~kAggSum, r);
-            if (ops & kAggSum) {
-                r[0] = (int64_t)acc.lo;
-                r[1] = (int64_t)acc.hi;
-            }
-        }
+        part.result(ops, type, base, from_slices, r);
         out[0] = r[0];
         out[1] = r[1];
         out[2] = r[2];
         out[3] = r[3];
-        out[4] = (int64_t)cv;
+        out[4] = (int64_t)part.valid;
         out[5] = (int64_t)workspace[(uint64_t)kAggPartial * kAggMaxGrid];
     }
 }
@@ -2607,21 +2610,15 @@ __global__ __launch_bounds__(512, 2) void eval_slice_select(EvalArgs a, SliceSel
     for (uint32_t i = blockIdx.x; i < n_idx; i += gridDim.x) {
         const uint64_t tile_word0 = (uint64_t)tile_at(a, i) * TILE_WORDS;
         uint64_t r[NW];
-        if constexpr (K > 0) {
-            u64x2 v[K][PAIRS];
-            load_tile<K, PAIRS, THREADS>(a, tile_word0, t, v);
-            eval_words<K, NW, FORM>(a.prog, v, r);
-        } else {
-#pragma unroll
-            for (int j = 0; j < NW; ++j) r[j] = ~0ull;
-        }
-        tail_mask<NW, THREADS>(a, tile_word0, t, r);
+        eval_tile<K, FORM, NW, THREADS>(a, tile_word0, t, r);
         u64x2 fv[PAIRS];
 #pragma unroll
         for (int p = 0; p < PAIRS; ++p) {
             fv[p].x = r[2 * p];
             fv[p].y = r[2 * p + 1];
         }
+        // (load_pair's words, spelled out: read through load_pair this kernel compiles to 132 VGPRs and
+        // three waves per SIMD in 13 instantiations that have four this way)
         if (g.validity) {
             if (tile_word0 + TILE_WORDS <= a.n_words) {  // uniform: the whole tile lies below the last word
 #pragma unroll
@@ -2829,20 +2826,6 @@ __global__ __launch_bounds__(256) void merge_ids_kernel(const int64_t* __restric
 // kGroupBatchMinMax with MINMAX (the ripple keeps 16 more registers per group): NG × 1 leaves with one
 // group column, NG/2 × 2 with TWO. Each group's rows are counted in its partials, so the kernel takes
 // no ticket. Traffic: (b + K [+ 1] + the launch's group leaves)·n/8 bytes over the live zones.
-template <int THREADS>
-__device__ __forceinline__ u64x2 load_group_leaf(const uint64_t* bv, bool neg, bool whole, uint64_t tile_word0, int p,
-                                                 int t, uint64_t n_words) {
-    u64x2 e;
-    if (whole) {  // uniform: the whole tile lies below the last word
-        e = reinterpret_cast<const u64x2*>(bv + tile_word0)[p * THREADS + t];
-    } else {  // the tile holding the last word: nothing at or past n_words is read
-        const uint64_t gw = word_index<THREADS>(tile_word0, 2 * p, t);
-        e.x = gw < n_words ? bv[gw] : 0ull;
-        e.y = gw + 1 < n_words ? bv[gw + 1] : 0ull;
-    }
-    return neg ? ~e : e;
-}
-
 // One chunk of CNT slices from `top` down for every live group. GUARD: the chunk may reach above the
 // index's slices (the slice count rounded up to the chunk), and a slice that does not exist reads as
 // zero: it adds nothing to a sum, leaves a non-empty candidate set as it is (bit 0 of the offset) and
@@ -2905,15 +2888,7 @@ __global__ __launch_bounds__(512, 2) void eval_slice_aggregate_grouped(EvalArgs 
     for (uint32_t i = blockIdx.x; i < n_idx; i += gridDim.x) {
         const uint64_t tile_word0 = (uint64_t)tile_at(a, i) * TILE_WORDS;
         uint64_t r[NW];
-        if constexpr (K > 0) {
-            u64x2 v[K][PAIRS];
-            load_tile<K, PAIRS, THREADS>(a, tile_word0, t, v);
-            eval_words<K, NW, FORM>(a.prog, v, r);
-        } else {
-#pragma unroll
-            for (int j = 0; j < NW; ++j) r[j] = ~0ull;
-        }
-        tail_mask<NW, THREADS>(a, tile_word0, t, r);
+        eval_tile<K, FORM, NW, THREADS>(a, tile_word0, t, r);
         const bool whole = tile_word0 + TILE_WORDS <= a.n_words;
         static_assert(PAIRS == 2, "the pair loop selects between two pairs");
         // one pair at a time (not unrolled: both pairs' masks and slices in flight do not fit the
@@ -2931,13 +2906,13 @@ __global__ __launch_bounds__(512, 2) void eval_slice_aggregate_grouped(EvalArgs 
                 for (int b = 0; b < 2; ++b) {
                     eb[b] = u64x2{0ull, 0ull};
                     if ((uint32_t)b < q.n2)
-                        eb[b] = load_group_leaf<THREADS>(q.e2[b], (q.neg2 >> b) & 1u, whole, tile_word0, p, t, a.n_words);
+                        eb[b] = load_pair<THREADS>(q.e2[b], (q.neg2 >> b) & 1u, whole, tile_word0, p, t, a.n_words);
                 }
 #pragma unroll
                 for (int x = 0; x < NA; ++x) {
                     u64x2 ea = {0ull, 0ull};
                     if ((uint32_t)x < q.n1)
-                        ea = f & load_group_leaf<THREADS>(q.e1[x], (q.neg1 >> x) & 1u, whole, tile_word0, p, t, a.n_words);
+                        ea = f & load_pair<THREADS>(q.e1[x], (q.neg1 >> x) & 1u, whole, tile_word0, p, t, a.n_words);
                     m[2 * x] = ea & eb[0];
                     m[2 * x + 1] = ea & eb[1];
                 }
@@ -2946,11 +2921,11 @@ __global__ __launch_bounds__(512, 2) void eval_slice_aggregate_grouped(EvalArgs 
                 for (int x = 0; x < NA; ++x) {
                     m[x] = u64x2{0ull, 0ull};
                     if ((uint32_t)x < q.n1)
-                        m[x] = f & load_group_leaf<THREADS>(q.e1[x], (q.neg1 >> x) & 1u, whole, tile_word0, p, t, a.n_words);
+                        m[x] = f & load_pair<THREADS>(q.e1[x], (q.neg1 >> x) & 1u, whole, tile_word0, p, t, a.n_words);
                 }
             }
             if (g.validity) {
-                const u64x2 vv = load_group_leaf<THREADS>(g.validity, false, whole, tile_word0, p, t, a.n_words);
+                const u64x2 vv = load_pair<THREADS>(g.validity, false, whole, tile_word0, p, t, a.n_words);
 #pragma unroll
                 for (int j = 0; j < NG; ++j) {
                     c_rows[j] += (uint64_t)(__popcll(m[j].x) + __popcll(m[j].y));
@@ -2997,51 +2972,20 @@ __global__ __launch_bounds__(512, 2) void eval_slice_aggregate_grouped(EvalArgs 
             }
         }
     }
-    // wave, then workgroup, per group: exact integer adds and unsigned min / max, so any order gives
-    // the same
+    // wave, then workgroup, per group
+    using Partial = AggPartial<true>;
+    static_assert(Partial::kSlots == kGroupPartial, "the grouped workspace holds whole partials");
     __shared__ uint64_t s_part[NWAVES][NG][kGroupPartial];
 #pragma unroll
     for (int j = 0; j < NG; ++j) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            U128 o;
-            o.lo = __shfl_xor(acc[j].lo, d, 64);
-            o.hi = __shfl_xor(acc[j].hi, d, 64);
-            acc[j] = u128_add(acc[j], o);
-            const uint64_t omn = __shfl_xor(mn[j], d, 64), omx = __shfl_xor(mx[j], d, 64);
-            mn[j] = omn < mn[j] ? omn : mn[j];
-            mx[j] = omx > mx[j] ? omx : mx[j];
-            c_rows[j] += __shfl_xor(c_rows[j], d, 64);
-            c_valid[j] += __shfl_xor(c_valid[j], d, 64);
-        }
-        if (lane == 0) {
-            s_part[wave][j][0] = acc[j].lo;
-            s_part[wave][j][1] = acc[j].hi;
-            s_part[wave][j][2] = mn[j];
-            s_part[wave][j][3] = mx[j];
-            s_part[wave][j][4] = c_valid[j];
-            s_part[wave][j][5] = c_rows[j];
-        }
+        Partial part{acc[j], mn[j], mx[j], c_valid[j], c_rows[j]};
+        part.wave_reduce();
+        if (lane == 0) part.store(s_part[wave][j]);
     }
     __syncthreads();
-    if (t < NG) {
-        U128 s{0, 0};
-        uint64_t lo = ~0ull, hi = 0, cv = 0, cr = 0;
-        for (int w = 0; w < NWAVES; ++w) {
-            s = u128_add(s, U128{s_part[w][t][0], s_part[w][t][1]});
-            lo = s_part[w][t][2] < lo ? s_part[w][t][2] : lo;
-            hi = s_part[w][t][3] > hi ? s_part[w][t][3] : hi;
-            cv += s_part[w][t][4];
-            cr += s_part[w][t][5];
-        }
-        int64_t* part = q.partials + ((uint64_t)t * gridDim.x + blockIdx.x) * kGroupPartial;
-        part[0] = (int64_t)s.lo;
-        part[1] = (int64_t)s.hi;
-        part[2] = (int64_t)lo;
-        part[3] = (int64_t)hi;
-        part[4] = (int64_t)cv;
-        part[5] = (int64_t)cr;
-    }
+    if (t < NG)
+        Partial::fold(&s_part[0][t][0], NWAVES, NG * kGroupPartial)
+            .store(q.partials + ((uint64_t)t * gridDim.x + blockIdx.x) * kGroupPartial);
 }
 
 // The column path per group: x / valid as aggregate_arrays_kernel's, and per group column the probed
@@ -3146,48 +3090,20 @@ __global__ __launch_bounds__(64) void aggregate_grouped_finish_kernel(const int6
     const uint32_t slot = blockIdx.x;
     const uint32_t group = identity ? slot : q.group[slot < kGroupBatchSum ? slot : 0];
     if (group == kNoGroup) return;
-    U128 acc{0, 0};
-    uint64_t mn = ~0ull, mx = 0, cv = 0, cr = 0;
-    for (int b = lane; b < nblocks; b += 64) {
-        const int64_t* part = partials + ((uint64_t)slot * nblocks + b) * kGroupPartial;
-        acc = u128_add(acc, U128{(uint64_t)part[0], (uint64_t)part[1]});
-        mn = (uint64_t)part[2] < mn ? (uint64_t)part[2] : mn;
-        mx = (uint64_t)part[3] > mx ? (uint64_t)part[3] : mx;
-        cv += (uint64_t)part[4];
-        cr += (uint64_t)part[5];
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        U128 o;
-        o.lo = __shfl_xor(acc.lo, d, 64);
-        o.hi = __shfl_xor(acc.hi, d, 64);
-        acc = u128_add(acc, o);
-        const uint64_t omn = __shfl_xor(mn, d, 64), omx = __shfl_xor(mx, d, 64);
-        mn = omn < mn ? omn : mn;
-        mx = omx > mx ? omx : mx;
-        cv += __shfl_xor(cv, d, 64);
-        cr += __shfl_xor(cr, d, 64);
-    }
+    using Partial = AggPartial<true>;
+    Partial part;
+    for (int b = lane; b < nblocks; b += 64) part.merge(Partial::load(partials + ((uint64_t)slot * nblocks + b) * kGroupPartial));
+    part.wave_reduce();
     if (lane == 0) {
         int64_t r[4] = {0, 0, 0, 0};
-        if (cv != 0) {
-            if (from_slices) {
-                slice_agg_combine(type, base, cv, acc, mn, mx, ops, r);
-            } else {
-                slice_agg_combine(type, INT64_MIN, cv, U128{0, 0}, mn, mx, ops & ~kAggSum, r);
-                if (ops & kAggSum) {
-                    r[0] = (int64_t)acc.lo;
-                    r[1] = (int64_t)acc.hi;
-                }
-            }
-        }
+        if (part.valid != 0) part.result(ops, type, base, from_slices, r);
         int64_t* o = out + (uint64_t)group * 6;
         o[0] = r[0];
         o[1] = r[1];
         o[2] = r[2];
         o[3] = r[3];
-        o[4] = (int64_t)cv;
-        o[5] = (int64_t)cr;
+        o[4] = (int64_t)part.valid;
+        o[5] = (int64_t)part.rows;
     }
 }
 
@@ -4681,6 +4597,18 @@ hipError_t dispatch_k_form(const EvalProgram& prog, const F& f) {
     }
 }
 
+// the same with the zero-leaf program (every row): f(0, FORM_CONJ)
+template <typename F>
+hipError_t dispatch_k0_form(const EvalProgram& prog, const F& f) {
+    if (prog.n_leaves != 0) return dispatch_k_form(prog, f);
+    f(std::integral_constant<int, 0>{}, std::integral_constant<int, FORM_CONJ>{});
+    return hipSuccess;
+}
+// the persistent grid of a slice kernel: wpc 512-thread workgroups per CU, no more than tiles
+unsigned slice_grid(uint32_t num_tiles, int n_cus, unsigned wpc) {
+    return std::max(1u, std::min<unsigned>(num_tiles, std::min<unsigned>(wpc * (unsigned)n_cus, kAggMaxGrid)));
+}
+
 // production decode (scripts/kbench.hip): the run-claimed kernel wherever a
 // workgroup walks three or more tiles — one claim per filled LDS stage instead of one per pair
 // (SF100-sized, 1 % / 0.75 % / 0.4 % selected at K = 1 / 2 / 3: 41 / 39 / 44 µs vs 46 / 50 / 57
@@ -4938,16 +4866,10 @@ hipError_t launch_eval_slice_aggregate(EvalArgs a, const SliceAggArgs& g, uint32
                                        int n_cus, int64_t* out, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
     if (g.n_slices > kMaxSlices || a.num_tiles == 0 || !g.workspace || !a.ticket) return hipErrorInvalidValue;
     a.count = agg_count_slot(g.workspace);
-    // persistent grid: two 512-thread workgroups per CU, as the fused sum's
-    const unsigned grid =
-        std::max(1u, std::min<unsigned>(a.num_tiles, std::min<unsigned>(2u * (unsigned)n_cus, kAggMaxGrid)));
-    hipError_t e = hipSuccess;
-    if (a.prog.n_leaves == 0)
-        launch_slice_aggregate_kf<0, FORM_CONJ>(a, g, ops, grid, stream, ev0, ev1);
-    else
-        e = dispatch_k_form(a.prog, [&](auto k, auto form) {
-            launch_slice_aggregate_kf<k.value, form.value>(a, g, ops, grid, stream, ev0, ev1);
-        });
+    const unsigned grid = slice_grid(a.num_tiles, n_cus, 2);  // two workgroups per CU, as the fused sum's
+    hipError_t e = dispatch_k0_form(a.prog, [&](auto k, auto form) {
+        launch_slice_aggregate_kf<k.value, form.value>(a, g, ops, grid, stream, ev0, ev1);
+    });
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(aggregate_finish_kernel, dim3(1), dim3(64), 0, stream, g.workspace, (int)grid, ops, type, base, 1,
@@ -4970,19 +4892,13 @@ hipError_t launch_slice_select(EvalArgs a, const SliceSelectArgs& g, int mode, u
                                hipEvent_t ev0, hipEvent_t ev1) {
     if (g.n_slices > kMaxSlices || a.num_tiles == 0 || !g.workspace || !g.cand || !a.ticket) return hipErrorInvalidValue;
     a.count = select_count_slot(g.workspace);
-    // persistent grid, as the aggregate's: two 512-thread workgroups per CU
-    const unsigned grid =
-        std::max(1u, std::min<unsigned>(a.num_tiles, std::min<unsigned>(2u * (unsigned)n_cus, kAggMaxGrid)));
+    const unsigned grid = slice_grid(a.num_tiles, n_cus, 2);  // as the aggregate's
     const uint32_t bits = g.n_slices, passes = select_passes(bits, kSelectChunk);
     if (n_passes) *n_passes = passes;
-    hipError_t e = hipSuccess;
-    if (a.prog.n_leaves == 0)
-        hipExtLaunchKernelGGL((eval_slice_select<0, FORM_CONJ>), dim3(grid), dim3(512), 0, stream, ev0, nullptr, 0, a, g);
-    else
-        e = dispatch_k_form(a.prog, [&](auto kk, auto form) {
-            hipExtLaunchKernelGGL((eval_slice_select<kk.value, form.value>), dim3(grid), dim3(512), 0, stream, ev0,
-                                  nullptr, 0, a, g);
-        });
+    hipError_t e = dispatch_k0_form(a.prog, [&](auto kk, auto form) {
+        hipExtLaunchKernelGGL((eval_slice_select<kk.value, form.value>), dim3(grid), dim3(512), 0, stream, ev0, nullptr, 0,
+                              a, g);
+    });
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return e;
     for (uint32_t p = 0; p < passes; ++p) {
@@ -5054,15 +4970,10 @@ hipError_t launch_eval_slice_aggregate_grouped(const EvalArgs& a, const SliceAgg
     if (g.n_slices > kMaxSlices || a.num_tiles == 0 || !q.partials || q.n2 > 2 || q.n1 == 0 ||
         q.n1 > (q.n2 ? limit / 2 : limit))
         return hipErrorInvalidValue;
-    // persistent grid: one 512-thread workgroup per CU at the kernel's register count
-    const unsigned grid = std::max(1u, std::min<unsigned>(a.num_tiles, std::min<unsigned>((unsigned)n_cus, kAggMaxGrid)));
-    hipError_t e = hipSuccess;
-    if (a.prog.n_leaves == 0)
-        launch_slice_aggregate_grouped_kf<0, FORM_CONJ>(a, g, q, minmax, grid, stream, ev0, ev1);
-    else
-        e = dispatch_k_form(a.prog, [&](auto k, auto form) {
-            launch_slice_aggregate_grouped_kf<k.value, form.value>(a, g, q, minmax, grid, stream, ev0, ev1);
-        });
+    const unsigned grid = slice_grid(a.num_tiles, n_cus, 1);  // one workgroup per CU at the kernel's register count
+    hipError_t e = dispatch_k0_form(a.prog, [&](auto k, auto form) {
+        launch_slice_aggregate_grouped_kf<k.value, form.value>(a, g, q, minmax, grid, stream, ev0, ev1);
+    });
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(aggregate_grouped_finish_kernel, dim3(limit), dim3(64), 0, stream, q.partials, (int)grid, q, 0, ops,

@@ -198,27 +198,43 @@ CUBIT_HD inline void slice_agg_combine(int type, int64_t base, uint64_t count_va
     slice_agg_combine(type, base, count_valid, slice_weighted_sum(counts, 64), min_off, max_off, ops, out);
 }
 
-// Which path cubit_table_aggregate takes: the slices (true) or scan + probe + reduce over the column.
-// force_slices / force_column: CUBIT_AGG_FROM_SLICES / _FROM_COLUMN (the caller has refused both
-// together, and FROM_SLICES without a usable index). Otherwise the path that moves fewer bytes:
-//   slices: every live row reads its bit of the b slices, the K program leaves and, when the column
-//           is nullable, its validity: (b + K + nullable)/8 bytes per live row;
+// The one byte count behind the path rules below: the slices (true) or scan + probe + reduce over
+// the column. force_slices / force_column: the caller's FROM_SLICES / FROM_COLUMN flag (it has
+// refused both together, and FROM_SLICES without a usable index). Otherwise the path that moves
+// fewer bytes:
+//   slices: slice_bits/8 bytes per live row — the bits of a row the slice path reads, summed over
+//           its launches or passes (each rule below counts its own);
 //   column: the scan reads K/8 bytes per live row; per estimated qualifying row the id is written and
-//           read (16 bytes), the probed value and its validity are written and read (16 bytes) and
-//           the gather moves one 128-byte line, but never more lines than the column has.
+//           read (16 bytes), for each probed column the value and its validity are written and read
+//           (16 bytes) and the gather moves one 128-byte line, but never more lines than that column
+//           has (elem_bytes: the probed columns' element sizes), and the reduction reads column_extra
+//           bytes more.
+// Every term is a whole number of eighths of a byte, and below 2^53 eighths (a partition of 2^36 rows
+// is far inside) the double sums are exact: the order of the terms cannot move a tie.
+// Correctness never depends on the choice.
+inline bool path_from_slices(bool force_slices, bool force_column, bool usable, uint64_t slice_bits, uint32_t k_leaves,
+                             uint64_t live_rows, uint64_t rows, uint64_t est_rows, const uint64_t* elem_bytes,
+                             uint32_t n_probed, double column_extra) {
+    if (force_column || !usable) return false;
+    if (force_slices) return true;
+    const double slices = (double)slice_bits / 8.0 * (double)live_rows;
+    double column = (double)k_leaves / 8.0 * (double)live_rows + (16.0 + column_extra) * (double)est_rows;
+    for (uint32_t i = 0; i < n_probed; ++i)
+        column += 16.0 * (double)est_rows + std::min(128.0 * (double)est_rows, (double)elem_bytes[i] * (double)rows);
+    return slices <= column;
+}
+
+// Which path cubit_table_aggregate takes (path_from_slices, one probed column):
+//   slices: every live row reads its bit of the b slices, the K program leaves and, when the column
+//           is nullable, its validity: (b + K + nullable)/8 bytes per live row.
 // The constants are derived from bytes alone and stay so: at 612 M rows the measured crossover
 // (scripts/slice_agg_timing.py, interpolated between its 1e-3 and 2 % points: about 0.9 % of the rows
 // for 12 slices, 1.6 % for 24) lies where this rule puts it (0.94 %, 1.9 %), DESIGN.md §3.
-// Correctness never depends on the choice.
 inline bool aggregate_from_slices(bool force_slices, bool force_column, bool usable, uint32_t bits, uint32_t k_leaves,
                                   bool nullable, uint64_t live_rows, uint64_t rows, uint64_t est_rows,
                                   uint64_t elem_bytes) {
-    if (force_column || !usable) return false;
-    if (force_slices) return true;
-    const double slices = (double)(bits + k_leaves + (nullable ? 1u : 0u)) / 8.0 * (double)live_rows;
-    const double gathered = std::min(128.0 * (double)est_rows, (double)elem_bytes * (double)rows);
-    const double column = (double)k_leaves / 8.0 * (double)live_rows + 32.0 * (double)est_rows + gathered;
-    return slices <= column;
+    return path_from_slices(force_slices, force_column, usable, bits + k_leaves + (nullable ? 1u : 0u), k_leaves, live_rows,
+                            rows, est_rows, &elem_bytes, 1, 0.0);
 }
 
 // ---- grouped aggregates (cubit_table_aggregate_grouped): GROUP BY one or two columns that carry an
@@ -306,25 +322,16 @@ inline std::vector<GroupBatch> split_group_batches(uint32_t n1, uint32_t n2, boo
     return plain;
 }
 
-// Which path cubit_table_aggregate_grouped takes: aggregate_from_slices extended by bytes alone.
+// Which path cubit_table_aggregate_grouped takes (path_from_slices; the value column and each group
+// column are probed: elem_bytes holds the value column's size, then each group column's):
 //   slices: each launch reads (b + K + nullable + its group leaves)/8 bytes per live row:
-//           slice_bits = that sum over the launches (group_batches_bits);
-//   column: the scan reads K/8 bytes per live row; per estimated qualifying row the id is written and
-//           read (16 bytes), and for the value column and each group column the probed value and its
-//           validity are written and read (16 bytes) and the gather moves one 128-byte line, but
-//           never more lines than that column has (elem_bytes: the value column's, then each group
-//           column's).
+//           slice_bits = that sum over the launches (group_batches_bits).
 // With no group column and one launch without group leaves this is aggregate_from_slices.
 inline bool grouped_from_slices(bool force_slices, bool force_column, bool usable, uint64_t slice_bits, uint32_t k_leaves,
                                 uint64_t live_rows, uint64_t rows, uint64_t est_rows, const uint64_t* elem_bytes,
                                 uint32_t n_probed) {
-    if (force_column || !usable) return false;
-    if (force_slices) return true;
-    const double slices = (double)slice_bits / 8.0 * (double)live_rows;
-    double column = (double)k_leaves / 8.0 * (double)live_rows + 16.0 * (double)est_rows;
-    for (uint32_t i = 0; i < n_probed; ++i)
-        column += 16.0 * (double)est_rows + std::min(128.0 * (double)est_rows, (double)elem_bytes[i] * (double)rows);
-    return slices <= column;
+    return path_from_slices(force_slices, force_column, usable, slice_bits, k_leaves, live_rows, rows, est_rows, elem_bytes,
+                            n_probed, 0.0);
 }
 
 // ---- selection by rank from a bit-sliced index (cubit_table_select; O'Neil & Quass 1997 §3)
@@ -432,30 +439,23 @@ CUBIT_HD inline void select_result(const SelectState& s, int type, int64_t base,
     out[5] = (int64_t)count_rows;
 }
 
-// Which path cubit_table_select takes, shaped like aggregate_from_slices: the slices (true) or scan +
-// probe + array select. By estimated bytes alone:
+// Which path cubit_table_select takes (path_from_slices, one probed column):
 //   slices: pass 0 reads the K leaves, the validity and its chunk and writes the candidates; each
 //           later pass reads and writes the candidates, reads the previous chunk again and the next:
 //           (K + nullable + 1 + 2b - d + 2·(passes - 1))/8 bytes per live row, d = the last chunk;
-//   column: the aggregate's scan + probe (K/8 per live row; 32 bytes and one 128-byte line per
-//           estimated qualifying row, never more lines than the column has), then 64/kSelectArrayBits
-//           passes over the probed values (8 bytes each).
+//   column: the aggregate's scan + probe, then 64/kSelectArrayBits passes over the probed values
+//           (8 bytes each).
 // The constants are derived from bytes alone and marked so: at 612 M rows (scripts/slice_select_timing.py,
 // DESIGN.md §3) the rule's crossover is 1.4 % of the rows for 12 slices and 3.1 % for 24, while the
 // slices measured faster from 1 % up (and slower at 1e-3): the array passes run well below the memory
-// rate the model charges them. Correctness never depends on the choice.
+// rate the model charges them.
 inline bool select_from_slices(bool force_slices, bool force_column, bool usable, uint32_t bits, uint32_t k_leaves,
                                bool nullable, uint64_t live_rows, uint64_t rows, uint64_t est_rows, uint64_t elem_bytes) {
-    if (force_column || !usable) return false;
-    if (force_slices) return true;
     const uint32_t passes = select_passes(bits, kSelectChunk);
     const uint32_t last = select_chunk_bits(bits, kSelectChunk, passes - 1);
-    const double per_row = (double)(k_leaves + (nullable ? 1u : 0u) + 1u + 2u * bits - last + 2u * (passes - 1));
-    const double slices = per_row / 8.0 * (double)live_rows;
-    const double gathered = std::min(128.0 * (double)est_rows, (double)elem_bytes * (double)rows);
-    const double column = (double)k_leaves / 8.0 * (double)live_rows + 32.0 * (double)est_rows + gathered +
-                          8.0 * (double)(64 / kSelectArrayBits) * (double)est_rows;
-    return slices <= column;
+    const uint32_t per_row = k_leaves + (nullable ? 1u : 0u) + 1u + 2u * bits - last + 2u * (passes - 1);
+    return path_from_slices(force_slices, force_column, usable, per_row, k_leaves, live_rows, rows, est_rows, &elem_bytes, 1,
+                            8.0 * (double)(64 / kSelectArrayBits));
 }
 
 // One past the last node of the subtree rooted at node i of a prefix-order node array, or -1 when

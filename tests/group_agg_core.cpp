@@ -126,6 +126,33 @@ static void batch_checks() {
 }
 
 // ---- the path rule
+// The rule as it stood before the three path rules shared one byte count, restated literally:
+// grouped_from_slices gives this answer at every point, ties included.
+static bool grouped_restated(bool force_slices, bool force_column, bool usable, uint64_t slice_bits, uint32_t k_leaves,
+                             uint64_t live_rows, uint64_t rows, uint64_t est_rows, const uint64_t* elem_bytes,
+                             uint32_t n_probed) {
+    if (force_column || !usable) return false;
+    if (force_slices) return true;
+    const double slices = (double)slice_bits / 8.0 * (double)live_rows;
+    double column = (double)k_leaves / 8.0 * (double)live_rows + 16.0 * (double)est_rows;
+    for (uint32_t i = 0; i < n_probed; ++i)
+        column += 16.0 * (double)est_rows + std::min(128.0 * (double)est_rows, (double)elem_bytes[i] * (double)rows);
+    return slices <= column;
+}
+// the least estimate in [0, rows] at which a monotone rule takes the slices (rows + 1: at none)
+template <typename F>
+static uint64_t crossover(uint64_t rows, const F& rule) {
+    if (rule(0)) return 0;
+    if (!rule(rows)) return rows + 1;
+    uint64_t lo = 0, hi = rows;  // rule(lo) is false, rule(hi) true
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (rule(mid)) hi = mid;
+        else lo = mid;
+    }
+    return hi;
+}
+
 static void path_rule_checks() {
     const uint64_t rows = 612ull << 20;
     const uint64_t eb[3] = {8, 4, 4};
@@ -152,7 +179,19 @@ static void path_rule_checks() {
                                       "slices without a usable index");
                                 CHECK(!grouped_from_slices(true, false, false, sb, k, live, rows, est, eb, 1 + ncols),
                                       "forced slices without a usable index");
+                                for (int f = 0; f < 8; ++f)
+                                    CHECK(grouped_from_slices(f & 1, f & 2, f & 4, sb, k, live, rows, est, eb, 1 + ncols) ==
+                                              grouped_restated(f & 1, f & 2, f & 4, sb, k, live, rows, est, eb, 1 + ncols),
+                                          "differs from the restated rule", (int64_t)est, bits, groups);
                             }
+                            // just below, at and just above the estimate where the restated rule turns
+                            const uint64_t x = crossover(rows, [&](uint64_t e) {
+                                return grouped_restated(false, false, true, sb, k, live, rows, e, eb, 1 + ncols);
+                            });
+                            for (uint64_t e : {x ? x - 1 : 0, x, x + 1})
+                                CHECK(grouped_from_slices(false, false, true, sb, k, live, rows, e, eb, 1 + ncols) ==
+                                          grouped_restated(false, false, true, sb, k, live, rows, e, eb, 1 + ncols),
+                                      "differs from the restated rule at its crossover", (int64_t)e, bits, groups);
                             const uint64_t est = rows / 50;
                             const bool s = grouped_from_slices(false, false, true, sb, k, live, rows, est, eb, 1 + ncols);
                             CHECK(prev_groups || !s, "not monotone in the group count", groups, bits, k);

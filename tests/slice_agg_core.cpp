@@ -131,6 +131,31 @@ static void combine_checks() {
     }
 }
 
+// The rule as it stood before the three path rules shared one byte count, restated literally:
+// aggregate_from_slices gives this answer at every point, ties included.
+static bool aggregate_restated(bool force_slices, bool force_column, bool usable, uint32_t bits, uint32_t k_leaves,
+                               bool nullable, uint64_t live_rows, uint64_t rows, uint64_t est_rows, uint64_t elem_bytes) {
+    if (force_column || !usable) return false;
+    if (force_slices) return true;
+    const double slices = (double)(bits + k_leaves + (nullable ? 1u : 0u)) / 8.0 * (double)live_rows;
+    const double gathered = std::min(128.0 * (double)est_rows, (double)elem_bytes * (double)rows);
+    const double column = (double)k_leaves / 8.0 * (double)live_rows + 32.0 * (double)est_rows + gathered;
+    return slices <= column;
+}
+// the least estimate in [0, rows] at which a monotone rule takes the slices (rows + 1: at none)
+template <typename F>
+static uint64_t crossover(uint64_t rows, const F& rule) {
+    if (rule(0)) return 0;
+    if (!rule(rows)) return rows + 1;
+    uint64_t lo = 0, hi = rows;  // rule(lo) is false, rule(hi) true
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (rule(mid)) hi = mid;
+        else lo = mid;
+    }
+    return hi;
+}
+
 static void path_rule_checks() {
     const uint64_t rows = 612ull << 20;
     for (uint32_t bits : {0u, 1u, 12u, 24u, 33u, 64u})
@@ -152,6 +177,22 @@ static void path_rule_checks() {
                             if (aggregate_from_slices(false, false, false, bits, k, nullable, live, rows, est, elem))
                                 die("slices without a usable index", (int)k, (int64_t)est, bits, live);
                             checks += 4;
+                            for (int f = 0; f < 8; ++f) {
+                                if (aggregate_from_slices(f & 1, f & 2, f & 4, bits, k, nullable, live, rows, est, elem) !=
+                                    aggregate_restated(f & 1, f & 2, f & 4, bits, k, nullable, live, rows, est, elem))
+                                    die("differs from the restated rule", f, (int64_t)est, bits, live);
+                                ++checks;
+                            }
+                        }
+                        // just below, at and just above the estimate where the restated rule turns
+                        const uint64_t x = crossover(rows, [&](uint64_t est) {
+                            return aggregate_restated(false, false, true, bits, k, nullable, live, rows, est, elem);
+                        });
+                        for (uint64_t est : {x ? x - 1 : 0, x, x + 1}) {
+                            if (aggregate_from_slices(false, false, true, bits, k, nullable, live, rows, est, elem) !=
+                                aggregate_restated(false, false, true, bits, k, nullable, live, rows, est, elem))
+                                die("differs from the restated rule at its crossover", (int)k, (int64_t)est, bits, live);
+                            ++checks;
                         }
                     }
     // from the bytes: a 12-bit column keeps its slices for a filter that keeps every row and gathers for one that

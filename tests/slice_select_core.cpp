@@ -240,6 +240,35 @@ static void pass_sequence() {
 }
 
 // ---- the path rule
+// The rule as it stood before the three path rules shared one byte count, restated literally:
+// select_from_slices gives this answer at every point, ties included.
+static bool select_restated(bool force_slices, bool force_column, bool usable, uint32_t bits, uint32_t k_leaves,
+                            bool nullable, uint64_t live_rows, uint64_t rows, uint64_t est_rows, uint64_t elem_bytes) {
+    if (force_column || !usable) return false;
+    if (force_slices) return true;
+    const uint32_t passes = select_passes(bits, kSelectChunk);
+    const uint32_t last = select_chunk_bits(bits, kSelectChunk, passes - 1);
+    const double per_row = (double)(k_leaves + (nullable ? 1u : 0u) + 1u + 2u * bits - last + 2u * (passes - 1));
+    const double slices = per_row / 8.0 * (double)live_rows;
+    const double gathered = std::min(128.0 * (double)est_rows, (double)elem_bytes * (double)rows);
+    const double column = (double)k_leaves / 8.0 * (double)live_rows + 32.0 * (double)est_rows + gathered +
+                          8.0 * (double)(64 / kSelectArrayBits) * (double)est_rows;
+    return slices <= column;
+}
+// the least estimate in [0, rows] at which a monotone rule takes the slices (rows + 1: at none)
+template <typename F>
+static uint64_t crossover(uint64_t rows, const F& rule) {
+    if (rule(0)) return 0;
+    if (!rule(rows)) return rows + 1;
+    uint64_t lo = 0, hi = rows;  // rule(lo) is false, rule(hi) true
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (rule(mid)) hi = mid;
+        else lo = mid;
+    }
+    return hi;
+}
+
 static void path_rule() {
     for (uint32_t bits : {0u, 1u, 4u, 12u, 24u, 64u})
         for (uint32_t k : {0u, 1u, 4u, 8u})
@@ -255,7 +284,19 @@ static void path_rule() {
                         CHECK(!select_from_slices(false, true, true, bits, k, nullable, live, rows, est, 8), "forced column");
                         CHECK(!select_from_slices(false, false, false, bits, k, nullable, live, rows, est, 8), "no index");
                         CHECK(!select_from_slices(true, false, false, bits, k, nullable, live, rows, est, 8), "no index, forced");
+                        for (int f = 0; f < 8; ++f)
+                            CHECK(select_from_slices(f & 1, f & 2, f & 4, bits, k, nullable, live, rows, est, 8) ==
+                                      select_restated(f & 1, f & 2, f & 4, bits, k, nullable, live, rows, est, 8),
+                                  "restated: bits %u k %u rows %" PRIu64 " est %" PRIu64 " flags %d", bits, k, rows, est, f);
                     }
+                    // just below, at and just above the estimate where the restated rule turns
+                    const uint64_t x = crossover(rows, [&](uint64_t est) {
+                        return select_restated(false, false, true, bits, k, nullable, live, rows, est, 8);
+                    });
+                    for (uint64_t est : {x ? x - 1 : 0, x, x + 1})
+                        CHECK(select_from_slices(false, false, true, bits, k, nullable, live, rows, est, 8) ==
+                                  select_restated(false, false, true, bits, k, nullable, live, rows, est, 8),
+                              "restated at the crossover: bits %u k %u rows %" PRIu64 " est %" PRIu64, bits, k, rows, est);
                 }
     // every row of a large partition: the slices; a handful of rows: the column
     CHECK(select_from_slices(false, false, true, 24, 2, true, 612000000, 612000000, 306000000, 4), "dense takes the slices");

@@ -317,6 +317,13 @@ def test_clustered_column_skips_zones(ctx):
         assert 0 < ev < nz == 4, (path, ev, nz)
         assert t.aggregate_by(1, [2], fs, path=path, zonemap=False) == skipped
         assert t.last_zones() == (nz, nz)
+    # the three queries answered from the slices plan alike: the same leaves, passes and zones
+    plans = []
+    for call in (lambda: t.aggregate(1, fs, path="slices"), lambda: t.quantile(1, 0.5, fs, path="slices"),
+                 lambda: t.aggregate_by(1, [2], fs, path="slices")):
+        call()
+        plans.append((t.last_plan(), t.last_zones()))
+    assert plans[0] == plans[1] == plans[2] and plans[0][1][0] < plans[0][1][1], plans
     t.close()
 
 
@@ -494,6 +501,18 @@ def test_errors(main, ctx):
     assert grouped(t.handle, None, 0, None, 99, cols, 2, L.AGG_SUM, out.ptr, 6) == L.ERR_INVALID
     assert grouped(t.handle, None, 0, None, B, cols, 2, L.AGG_SUM, out.ptr, 6) == L.OK
     t.ctx.check()
+    # two faults at once: the earlier check answers
+    both = L.AGG_SUM | L.AGG_FROM_SLICES | L.AGG_FROM_COLUMN
+    assert grouped(t.handle, None, 0, None, 99, cols, 2, both, out.ptr, 6) == L.ERR_INVALID
+    assert b"both" in t.lib.cubit_last_error()
+    assert grouped(t.handle, None, 0, None, 99, cols, 2, 8, out.ptr, 6) == L.ERR_INVALID
+    assert b"ops 8" in t.lib.cubit_last_error()
+    unindexed = (C.c_int * 2)(G3, A)  # A has no EQUALITY index, and one slot is no room for the groups
+    assert grouped(t.handle, None, 0, None, B, unindexed, 2, L.AGG_SUM, out.ptr, 1) == L.ERR_UNSUPPORTED
+    assert b"column 0" in t.lib.cubit_last_error()
+    with pytest.raises(L.CubitError) as e:  # no sliced index, and a filter no row passes: refused, no zeros
+        t.aggregate_by(E, [G3], FILTERS["false"][0], FILTERS["false"][1], path="slices")
+    assert e.value.code == L.ERR_INVALID and b"column 4" in t.lib.cubit_last_error()
     out.free()
     # more than 256 groups: 17 x 16 slots
     rng = np.random.default_rng(57)

@@ -244,6 +244,14 @@ def test_refusals(typed):
     assert agg(t.handle, None, 0, None, 0, 8, out.ptr) == L.ERR_INVALID
     assert agg(t.handle, None, 0, None, 4, L.AGG_SUM | L.AGG_FROM_SLICES, out.ptr) == L.ERR_INVALID  # no slices
     assert t.aggregate(4) == t.aggregate(4, path="column") and not t.last_aggregate_from_slices()
+    # two faults at once: the earlier check answers
+    both = L.AGG_SUM | L.AGG_FROM_SLICES | L.AGG_FROM_COLUMN
+    assert agg(t.handle, None, 0, None, 99, both, out.ptr) == L.ERR_INVALID and b"both" in t.lib.cubit_last_error()
+    assert agg(t.handle, None, 0, None, 99, 8, out.ptr) == L.ERR_INVALID and b"ops 8" in t.lib.cubit_last_error()
+    with pytest.raises(L.CubitError) as e:  # no sliced index, and a filter no row passes: refused, no zeros
+        t.aggregate(4, FILTERS["false"][0], path="slices")
+    assert e.value.code == L.ERR_INVALID and b"column 4" in t.lib.cubit_last_error()
+    out.free()
 
 
 # ------------------------------------------------------------------ zonemaps

@@ -162,6 +162,13 @@ def test_refusals(table):
     assert sel(t.handle, None, 0, None, 0, 3, 0, 0.0, 0, out.ptr) == L.ERR_INVALID  # mode
     assert sel(t.handle, None, 0, None, 0, 0, 0, 0.0, L.SELECT_FROM_SLICES | L.SELECT_FROM_COLUMN, out.ptr) == L.ERR_INVALID
     assert sel(t.handle, None, 0, None, 0, 0, 0, 0.0, 8, out.ptr) == L.ERR_INVALID  # flags
+    # two faults at once: the earlier check answers
+    both = L.SELECT_FROM_SLICES | L.SELECT_FROM_COLUMN
+    assert sel(t.handle, None, 0, None, 99, 0, 0, 0.0, both, out.ptr) == L.ERR_INVALID and b"both" in t.lib.cubit_last_error()
+    assert sel(t.handle, None, 0, None, 99, 0, 0, 0.0, 8, out.ptr) == L.ERR_INVALID and b"flags 8" in t.lib.cubit_last_error()
+    with pytest.raises(L.CubitError) as e:  # no sliced index, and a filter no row passes: refused, no zeros
+        t.quantile(1, 0.5, FILTERS["false"][0], path="slices")
+    assert e.value.code == L.ERR_INVALID and b"column 1" in t.lib.cubit_last_error()
     # without a sliced index the unforced call and the column path agree
     assert t.quantile(1, 0.5) == t.quantile(1, 0.5, path="column") and not t.last_select()[0]
     t.use_sliced(False)
