@@ -1174,6 +1174,7 @@ struct cubit_table {
     size_t scratch_used = 0;
     std::unique_ptr<DevBuf> ones;  // all valid rows
     uint32_t last_leaves = 0, last_passes = 0;
+    uint32_t last_form = 0;  // eval_form of the last planned program (FORM_*), 0 with last_leaves
     // the last planned program, when it is one table-owned index bitvector as it stands (no
     // complement, no patch): its per-zone counts give the decode its offsets up front
     const uint64_t* single_leaf = nullptr;
@@ -5007,7 +5008,7 @@ int plan_program(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_node
     }
     if (e->kind == Expr::CONST_FALSE) {
         *empty = true;
-        t->last_leaves = 0;
+        t->last_leaves = t->last_form = 0;
         return CUBIT_OK;
     }
     if (e->kind == Expr::CONST_TRUE) {
@@ -5022,7 +5023,7 @@ int plan_program(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_node
         if (int rc = zone_plan(t, e, *live, &none)) return rc;
         if (none) {
             *empty = true;
-            t->last_leaves = 0;
+            t->last_leaves = t->last_form = 0;
             return CUBIT_OK;
         }
     }
@@ -5032,6 +5033,7 @@ int plan_program(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_node
     em.emit_top(e);
     if (!em.ok) return fail(CUBIT_ERR_UNSUPPORTED, "program does not fit one pass");
     t->last_leaves = em.prog.n_leaves;
+    t->last_form = eval_form(em.prog);
     t->last_passes++;
     t->single_leaf = e->kind == Expr::LEAF && !e->neg && e->leaf.zsrc == kZoneBits && !e->leaf.zbv &&
                              e->leaf.zdirty < 0 && em.prog.n_leaves == 1 && em.prog.negate == 0
@@ -5167,7 +5169,7 @@ extern "C" int cubit_table_scan(cubit_table* t, const cubit_filter_node* nodes, 
     t->ctx->last_tiles = 0;  // until this scan's decode is launched (a planning error leaves none)
     t->ctx->last_from_list = false;
     if (t->n_rows == 0) {  // empty partition
-        t->last_leaves = t->last_passes = 0;
+        t->last_leaves = t->last_passes = t->last_form = 0;
         t->last_live = t->last_zones = 0;
         HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(uint64_t), t->ctx->stream));
         return CUBIT_OK;
@@ -5298,7 +5300,7 @@ int bind_slices(cubit_table* t, const cubit_txn* txn, int col, const Column& c, 
 int plan_slice_query(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_nodes, const cubit_txn* txn, bool zonemap,
                      SlicePlan& p) {
     if (t->n_rows == 0) {
-        t->last_leaves = t->last_passes = 0;
+        t->last_leaves = t->last_passes = t->last_form = 0;
         t->last_live = t->last_zones = 0;
         t->last_sliced = 0;
         p.no_rows = true;
@@ -5879,6 +5881,13 @@ extern "C" int cubit_table_last_plan(cubit_table* t, uint32_t* n_leaves, uint32_
     CUBIT_LOCK(t->ctx);
     if (n_leaves) *n_leaves = t->last_leaves;
     if (n_passes) *n_passes = t->last_passes;
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_last_form(cubit_table* t, uint32_t* form) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    if (form) *form = t->last_form;
     return CUBIT_OK;
 }
 

@@ -69,6 +69,7 @@ SCAN_CHECK_CAPACITY = 4  # synchronise; ERR_CAPACITY when the count exceeds the 
 SCAN_NO_ZONEMAP = 8  # evaluate every zone (the zonemap skip off; results are identical)
 DECODE_AUTO, DECODE_PAIRS, DECODE_RUNS, DECODE_LOOKBACK = 0, 1, 2, 3
 DECODE_PREFIXED = 4  # reported only (cubit_ctx_last_decode_kernel): one index bitvector, offsets from its zone counts
+FORM_POSTFIX, FORM_CONJ, FORM_DNF, FORM_CNF = range(4)  # cubit_table_last_form: the kernel template the last program ran in
 
 
 class FilterNode(C.Structure):
@@ -181,6 +182,7 @@ GPU_SIGNATURES = {
     "cubit_table_probe": (C.c_int, [_P, C.c_int, C.POINTER(Txn), _P, _P, _U64, _P]),
     "cubit_table_probe_validity": (C.c_int, [_P, C.c_int, C.POINTER(Txn), _P, _P, _U64, _P, _P]),
     "cubit_table_last_plan": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U32)]),
+    "cubit_table_last_form": (C.c_int, [_P, C.POINTER(_U32)]),
     "cubit_table_set_derived_budget": (C.c_int, [_P, _U64]),
     "cubit_table_derived_stats": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U64), C.POINTER(_U64)]),
     "cubit_table_set_derived_chain_cost": (C.c_int, [_P, _U64]),

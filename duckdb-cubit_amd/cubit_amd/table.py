@@ -929,6 +929,13 @@ class CubitTable:
         L.check(self.lib.cubit_table_last_plan(self.handle, C.byref(k), C.byref(p)))
         return int(k.value), int(p.value)
 
+    def last_form(self) -> int:
+        """The form of the last planned program (L.FORM_POSTFIX / FORM_CONJ / FORM_DNF / FORM_CNF): with
+        last_plan()'s leaf count, the kernel instantiation that ran. 0 when the filter folded to FALSE."""
+        f = C.c_uint32()
+        L.check(self.lib.cubit_table_last_form(self.handle, C.byref(f)))
+        return int(f.value)
+
     def set_derived_budget(self, n_bytes: int) -> None:
         """Bytes the kept leaf combinations (derived leaves) may hold; 0 turns them off."""
         L.check(self.lib.cubit_table_set_derived_budget(self.handle, int(n_bytes)))

@@ -691,6 +691,12 @@ int cubit_table_probe_validity(cubit_table *t, int col, const cubit_txn *txn, co
 int cubit_table_estimate_rows(cubit_table *t, const cubit_filter_node *nodes, uint32_t n_nodes, uint64_t *rows);
 /* Bitvectors the last cubit_table_scan read per 64-row word (K) — for roofline bytes. */
 int cubit_table_last_plan(cubit_table *t, uint32_t *n_leaves, uint32_t *n_passes);
+/* The evaluation form of the last planned program, the kernel template its n_leaves run in:
+ * 0 = POSTFIX (the general interpreter), 1 = CONJ (an AND of literals), 2 = DNF (an OR of ANDs of
+ * literals), 3 = CNF (an AND of ORs of literals). 0 as well when the filter folded to FALSE or the
+ * partition is empty (n_leaves is 0 then). With cubit_table_last_plan it names the (leaf count,
+ * form) instantiation that ran — for tests; results never depend on it. */
+int cubit_table_last_form(cubit_table *t, uint32_t *form);
 /* Derived leaves. A combination of one column's index / validity bitvectors that scans keep asking
  * for — a RANGE interval's L(hi) AND NOT L(lo), the union behind an IN-list on an EQUALITY index or
  * a range over BINS — is evaluated once and kept as one table-owned bitvector, which later plans

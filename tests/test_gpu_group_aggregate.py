@@ -103,10 +103,11 @@ def expected(ocols, col, typ, by, plan, n, tx, ops, codes=None, keyfn=None):
 
 
 def check_groups(t, ocols, col, typ, by, n, fs=None, residual=None, txn=None, tx=None, ops=None, zonemap=True,
-                 paths=PATHS, codes=None, keyfn=None, what=None):
+                 paths=PATHS, codes=None, keyfn=None, what=None, after=None):
     """Every path equals the expected dict, last_grouped names the path that ran, and the groups add up
     to count() and aggregate() of the same filter. Returns (the expected dict, whether path=None read
-    the slices)."""
+    the slices). after(path) runs behind each aggregate_by, while the table's last_* counters are still
+    that call's."""
     if ops is None:
         ops = L.AGG_ALL if typ not in (L.TYPE_DOUBLE, L.TYPE_VARCHAR) else L.AGG_MIN | L.AGG_MAX
     want, n_ids = expected(ocols, col, typ, by, F.serialize(fs, residual), n, tx, ops, codes, keyfn)
@@ -114,6 +115,8 @@ def check_groups(t, ocols, col, typ, by, n, fs=None, residual=None, txn=None, tx
     for path in paths:
         got = t.aggregate_by(col, by, fs, residual, txn=txn, ops=ops, path=path, zonemap=zonemap)
         assert got == want, (what, col, by, path, ops, got, want)
+        if after:
+            after(path)
         used, n_groups, launches = t.last_grouped()
         assert n_groups == len(t.aggregate_groups(by)) >= len(want)
         assert (launches > 0) == used or not want

@@ -85,8 +85,9 @@ def expected(ocols, col, typ, plan, n, tx, ops, codes=None):
 
 
 def check_paths(t, ocols, col, typ, n, fs=None, residual=None, txn=None, tx=None, ops=None, zonemap=True,
-                paths=PATHS, codes=None, what=None):
-    """Every path equals the expected reduction; returns whether path=None read the slices."""
+                paths=PATHS, codes=None, what=None, after=None):
+    """Every path equals the expected reduction; returns whether path=None read the slices. after(path)
+    runs behind each call, while the table's last_* counters are still that call's."""
     if ops is None:
         ops = L.AGG_ALL if typ not in (L.TYPE_DOUBLE, L.TYPE_VARCHAR) else L.AGG_MIN | L.AGG_MAX
     want = expected(ocols, col, typ, F.serialize(fs, residual), n, tx, ops, codes)
@@ -94,6 +95,8 @@ def check_paths(t, ocols, col, typ, n, fs=None, residual=None, txn=None, tx=None
     for path in paths:
         got = t.aggregate(col, fs, residual, txn=txn, ops=ops, path=path, zonemap=zonemap)
         assert got == want, (what, col, path, ops, got, want)
+        if after:
+            after(path)
         used = t.last_aggregate_from_slices()
         if path is None:
             chose = used

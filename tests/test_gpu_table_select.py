@@ -56,18 +56,26 @@ def oracle_keys(ocols, col, fs, residual, n, tx=None):
 
 
 def check_select(t, s, count_rows, col, fs=None, residual=None, txn=None, paths=PATHS, zonemaps=(True, False),
-                 to_value=int, what=None):
+                 to_value=int, what=None, ranks=None, quantiles=QUANTILES, after=None):
+    """kth at `ranks` (default: both ends, the middle and one past the last) in both directions and
+    quantile at `quantiles`, on every path with the zonemap as listed, against the ascending keys s.
+    after(path, zonemap) runs behind each call, while the table's last_* counters are still that call's."""
     m = len(s)
-    ranks = sorted({0, 1, m // 2, max(m - 2, 0), max(m - 1, 0), m})
+    if ranks is None:
+        ranks = sorted({0, 1, m // 2, max(m - 2, 0), max(m - 1, 0), m})
     for path in paths:
         for zm in zonemaps:
             for rank in ranks:
                 for desc in (False, True):
                     got = t.kth(col, rank, desc, fs, residual, txn=txn, path=path, zonemap=zm)
                     assert got == want(s, count_rows, desc, rank, to_value), (what, path, zm, rank, desc)
-            for q in QUANTILES:
+                    if after:
+                        after(path, zm)
+            for q in quantiles:
                 got = t.quantile(col, q, fs, residual, txn=txn, path=path, zonemap=zm)
                 assert got == want(s, count_rows, False, quantile_rank(m, q) if m else 0, to_value), (what, path, zm, q)
+                if after:
+                    after(path, zm)
             if path is not None and count_rows:  # (a filter that folds to FALSE runs neither path)
                 assert t.last_select()[0] == (path == "slices"), (what, path)
 
