@@ -4777,7 +4777,10 @@ int derive_chain(cubit_table* t, const DerivedKey& key, const std::vector<ExprP>
     std::sort(bvs.begin(), bvs.end());
     const uint64_t k = std::unique(bvs.begin(), bvs.end()) - bvs.begin();
     const uint64_t bytes = std::max<uint64_t>(t->cap_words, 1) * 8;
-    if (!t->derived.request(key, bytes, k)) return CUBIT_OK;
+    // priced by what this admission would pay: a block waiting in the pool (one of another size is no
+    // such block: it goes now, as alloc_derived_bv would send it), or a device allocation
+    size_bv_pool(t);
+    if (!t->derived.request(key, bytes, k, t->bv_pool.free_blocks() > 0)) return CUBIT_OK;
     Leaf l;
     l.zsrc = kZoneBits;
     l.pred = 3;
@@ -5930,6 +5933,13 @@ extern "C" int cubit_table_set_derived_chain_cost(cubit_table* t, uint64_t fixed
     if (!t) return fail(CUBIT_ERR_INVALID, "null table");
     CUBIT_LOCK(t->ctx);
     t->derived.set_chain_cost(fixed_bytes);
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_set_derived_chain_cost_pooled(cubit_table* t, uint64_t fixed_bytes) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null table");
+    CUBIT_LOCK(t->ctx);
+    t->derived.set_chain_cost_pooled(fixed_bytes);
     return CUBIT_OK;
 }
 

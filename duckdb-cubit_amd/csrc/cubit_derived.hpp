@@ -121,15 +121,28 @@ inline bool derived_chain_admit(uint64_t uses_so_far, uint64_t k, uint64_t B, ui
     return (u128)uses_so_far * (k - 1) * B >= (u128)(k + 1) * B + F;
 }
 
-// F unless cubit_table_set_derived_chain_cost says otherwise, measured on an MI355X at TPC-H SF100
-// (DESIGN.md §3): the scan that admitted the l_discount interval took 413 µs longer than the plain
-// scans after it, 38 µs of them the bits-only pass's own 225 MB; the other 376 µs at the 5.97 TB/s
-// of that scan's byte mix. SF100 Q6 (k = 3, B = 75 MB) is bought at its 18th request; a 300,001-row
-// table (B = 131 KB as allocated) would need some 8,500. That scan allocated its block; an admitting
-// scan that takes a block of the table's pool (cubit_row_list.hpp) measures 0.196 GB
-// (profiles/r15_admission_cost.txt). The constant stays at the allocating scan's cost, which a table's
-// first admission still pays: tests/derived_chain_core.cpp pins the admission points it gives.
+// F has two values, for the two admitting scans there are. Either is what the cache starts
+// with; cubit_table_set_derived_chain_cost replaces both, cubit_table_set_derived_chain_cost_pooled the
+// second alone.
+//
+// kDerivedChainCost: the admitting scan allocates its block, as a table's first admission does. Measured
+// on an MI355X at TPC-H SF100 (profiles/r13_admission_cost.txt): the scan that admitted the l_discount
+// interval took 413 µs longer than the plain scans after it, 38 µs of them the bits-only pass's own
+// 225 MB; the other 376 µs at the 5.97 TB/s of that scan's byte mix. With it SF100 Q6 (k = 3, B = 75 MB)
+// is bought at its 18th request; a 300,001-row table (B = 131 KB as allocated) would need some 8,500.
+// tests/derived_chain_core.cpp pins the admission points it gives.
+//
+// kDerivedChainCostPooled: the admitting scan takes a block that waits in the table's pool
+// (cubit_row_list.hpp), as every admission after the table's first does while the budget holds a second
+// block, and every re-admission after a write. Measured the same way (profiles/r19_admission_cost.txt):
+// over 12 pooled admissions at SF100 the admitting scan took 133.0 µs against 65.7 µs for the plain K = 3
+// scans before it, 50.3 µs of the difference the bits-only pass's own 300 MB, the other 17 µs at 5.97 TB/s
+// 0.101 GB (0.087-0.193; 0.179 GB on an SF100 / 8 partition, where the same microseconds weigh more beside
+// a smaller pass). With it SF100 Q6 from a pooled block is bought at its 4th request (with the interval,
+// whose slab fills the pool in that plan), an SF100 / 8 partition at its 9th, and the 300,001-row table
+// still needs some 385: a one-off query keeps paying nothing.
 constexpr uint64_t kDerivedChainCost = 2'240'000'000ull;
+constexpr uint64_t kDerivedChainCostPooled = 100'000'000ull;
 
 // The cache of materialised combinations (payload P: whatever owns the bitvector) and the use
 // counters of those not materialised yet.
@@ -150,9 +163,14 @@ class DerivedCache {
     uint64_t hits() const { return hits_; }  // of both kinds
     size_t chain_size() const { return chains_; }
     uint64_t chain_hits() const { return chain_hits_; }
+    // F of derived_chain_admit for an admission that allocates its block, and for one that takes a
+    // pooled block
     uint64_t chain_cost() const { return chain_cost_; }
-    // F of derived_chain_admit; counters keep counting under the new value
-    void set_chain_cost(uint64_t fixed_bytes) { chain_cost_ = fixed_bytes; }
+    uint64_t chain_cost_pooled() const { return chain_cost_pooled_; }
+    // Both costs at once (the override: 0 = the count rule, UINT64_MAX = never), or the pooled one
+    // alone; counters keep counting under the new value
+    void set_chain_cost(uint64_t fixed_bytes) { chain_cost_ = chain_cost_pooled_ = fixed_bytes; }
+    void set_chain_cost_pooled(uint64_t fixed_bytes) { chain_cost_pooled_ = fixed_bytes; }
     size_t counters() const { return uses_.size(); }
     bool in_plan() const { return in_plan_; }
 
@@ -187,8 +205,9 @@ class DerivedCache {
     // when it is to be materialised now: the admission rule holds and the budget has room. When
     // only room is missing, the least recently used entries go at the next begin_plan and a
     // later request is admitted. A chain key passes k, the leaves the plan reads in its place at
-    // this moment (after the column groups took theirs), and is admitted by cost.
-    bool request(const DerivedKey& key, uint64_t entry_bytes, uint64_t k = 0) {
+    // this moment (after the column groups took theirs), and is admitted by cost: the pooled cost
+    // when the caller says the block this admission would take is waiting, else the allocating one.
+    bool request(const DerivedKey& key, uint64_t entry_bytes, uint64_t k = 0, bool pooled = false) {
         if (budget_ == 0 || entry_bytes > budget_) return false;
         auto it = uses_.find(key);
         if (it == uses_.end()) {
@@ -196,7 +215,8 @@ class DerivedCache {
             it = uses_.emplace(key, 0).first;
         }
         const uint64_t uses_so_far = it->second++;
-        if (derived_is_chain(key) ? !derived_chain_admit(uses_so_far, k, entry_bytes, chain_cost_)
+        const uint64_t cost = pooled ? chain_cost_pooled_ : chain_cost_;
+        if (derived_is_chain(key) ? !derived_chain_admit(uses_so_far, k, entry_bytes, cost)
                                   : !derived_admit(uses_so_far, key.lits.size()))
             return false;
         if (bytes_ + entry_bytes > budget_) {
@@ -263,6 +283,7 @@ class DerivedCache {
     uint64_t chain_hits_ = 0;
     size_t chains_ = 0;  // entries with a chain key
     uint64_t chain_cost_ = kDerivedChainCost;
+    uint64_t chain_cost_pooled_ = kDerivedChainCostPooled;
     uint64_t want_ = 0;  // room a declined admission asked for
     bool in_plan_ = false;
     std::list<Entry> lru_;  // front = most recently used

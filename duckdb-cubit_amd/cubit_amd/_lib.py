@@ -186,6 +186,7 @@ GPU_SIGNATURES = {
     "cubit_table_set_derived_budget": (C.c_int, [_P, _U64]),
     "cubit_table_derived_stats": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U64), C.POINTER(_U64)]),
     "cubit_table_set_derived_chain_cost": (C.c_int, [_P, _U64]),
+    "cubit_table_set_derived_chain_cost_pooled": (C.c_int, [_P, _U64]),
     "cubit_table_derived_chain_stats": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U64)]),
     "cubit_table_derived_pool_stats": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(_U64)]),
     "cubit_table_use_row_lists": (C.c_int, [_P, C.c_int]),

@@ -950,8 +950,14 @@ class CubitTable:
 
     def set_derived_chain_cost(self, fixed_bytes: int) -> None:
         """The fixed cost of a scan that admits a chain (a conjunction over several columns kept as one
-        leaf), in bytes; 0 = admit by count like a column group, 2**64 - 1 = never."""
+        leaf), in bytes; 0 = admit by count like a column group, 2**64 - 1 = never. Sets both costs: of a scan
+        that allocates the chain's block and of one that takes a pooled block."""
         L.check(self.lib.cubit_table_set_derived_chain_cost(self.handle, int(fixed_bytes)))
+
+    def set_derived_chain_cost_pooled(self, fixed_bytes: int) -> None:
+        """That cost for an admitting scan that finds a free block in the table's pool (derived_pool_stats),
+        alone; set_derived_chain_cost afterwards replaces it again."""
+        L.check(self.lib.cubit_table_set_derived_chain_cost_pooled(self.handle, int(fixed_bytes)))
 
     def derived_chain_stats(self):
         """(kept chains, chains replaced by one leaf so far); both are part of derived_stats too."""

@@ -718,8 +718,17 @@ int cubit_table_derived_stats(cubit_table *t, uint32_t *leaves, uint64_t *bytes,
  * plan reads in the chain's place, fixed_bytes the fixed cost of an admitting scan expressed in bytes
  * (default: measured, cubit_derived.hpp). A small table needs thousands of requests, so a one-off
  * query pays nothing. 0 makes it the count rule of the column groups; UINT64_MAX never keeps a
- * chain (kept ones stay until evicted or invalidated). */
+ * chain (kept ones stay until evicted or invalidated).
+ * There are two such costs, and this call sets both to fixed_bytes: that of an admitting scan which
+ * allocates the chain's block (a table's first admission; a table whose budget holds one block), and
+ * that of one which takes a block waiting in the table's free list (cubit_table_derived_pool_stats:
+ * every later admission, and every re-admission after a write to the table). A request is priced by
+ * whether a block is waiting at that moment; its counter is the same under either cost. */
 int cubit_table_set_derived_chain_cost(cubit_table *t, uint64_t fixed_bytes);
+/* The cost of an admitting scan that takes a waiting block, alone (default: measured, about a tenth of
+ * the allocating scan's; cubit_derived.hpp). The allocating cost stays as it is; a later
+ * cubit_table_set_derived_chain_cost replaces both again. 0 and UINT64_MAX mean what they mean there. */
+int cubit_table_set_derived_chain_cost_pooled(cubit_table *t, uint64_t fixed_bytes);
 /* Kept chains (counted in cubit_table_derived_stats' leaves and bytes too) and the chains that plans
  * replaced by one leaf so far (counted in its hits too). Any pointer may be NULL. */
 int cubit_table_derived_chain_stats(cubit_table *t, uint32_t *chains, uint64_t *hits);
