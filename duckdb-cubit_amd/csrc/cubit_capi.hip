@@ -860,6 +860,52 @@ int cubit_bitslice_aggregate(cubit_ctx* ctx, const uint64_t* const* d_slices, ui
     return CUBIT_OK;
 }
 
+int cubit_bitslice_sum_product(cubit_ctx* ctx, const uint64_t* const* d_a_slices, uint32_t n_a,
+                               const uint64_t* d_a_validity, int64_t base_a, const uint64_t* const* d_b_slices,
+                               uint32_t n_b, const uint64_t* d_b_validity, int64_t base_b, const uint64_t* d_filter,
+                               uint64_t n_rows, int64_t* d_out) {
+    if (!ctx || !d_out || (n_a && !d_a_slices) || (n_b && !d_b_slices)) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(ctx);
+    if (n_a > kMaxSlices || n_b > kMaxSlices) return fail(CUBIT_ERR_INVALID, "%u and %u slices (0 … 64)", n_a, n_b);
+    if (n_rows >= (1ull << 47)) return fail(CUBIT_ERR_INVALID, "%llu rows exceed 2^47", (unsigned long long)n_rows);
+    auto aligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    if (!aligned(d_filter) || !aligned(d_a_validity) || !aligned(d_b_validity))
+        return fail(CUBIT_ERR_INVALID, "bitvectors must be 16-byte aligned");
+    // the operand with fewer slices is the inner one (the sum is symmetric)
+    const bool a_outer = n_a >= n_b;
+    SliceProductArgs g{};
+    for (uint32_t s = 0; s < n_a; ++s) {
+        if (!d_a_slices[s] || !aligned(d_a_slices[s])) return fail(CUBIT_ERR_INVALID, "slice %u of a is null or unaligned", s);
+        (a_outer ? g.outer : g.inner).s[s] = const_cast<uint64_t*>(d_a_slices[s]);
+    }
+    for (uint32_t s = 0; s < n_b; ++s) {
+        if (!d_b_slices[s] || !aligned(d_b_slices[s])) return fail(CUBIT_ERR_INVALID, "slice %u of b is null or unaligned", s);
+        (a_outer ? g.inner : g.outer).s[s] = const_cast<uint64_t*>(d_b_slices[s]);
+    }
+    if (int rc = set_device(ctx)) return rc;
+    if (n_rows == 0) {  // no rows: a zero sum and zero counts, nothing to launch
+        HIP_CHECK(hipMemsetAsync(d_out, 0, 4 * sizeof(int64_t), ctx->stream));
+        return CUBIT_OK;
+    }
+    g.n_outer = a_outer ? n_a : n_b;
+    g.n_inner = a_outer ? n_b : n_a;
+    g.valid_a = d_a_validity;
+    g.valid_b = d_b_validity;
+    g.workspace = ctx->agg;
+    EvalProgram prog{};
+    if (d_filter) {  // a one-leaf program; NULL: the zero-leaf form, every row below n_rows
+        prog.leaf[0] = d_filter;
+        prog.n_leaves = 1;
+    }
+    EvalArgs a;
+    if (int rc = tile_eval_args(ctx, prog, n_rows, 0, kAggTileWords, {}, a)) return rc;
+    hipEvent_t e0, e1;
+    if (int rc = timing_events(ctx, e0, e1)) return rc;
+    HIP_CHECK(launch_eval_slice_sum_product(a, g, a_outer ? base_a : base_b, a_outer ? base_b : base_a, ctx->n_cus, d_out,
+                                            4, nullptr, ctx->stream, e0, e1));
+    return CUBIT_OK;
+}
+
 int cubit_bitslice_select(cubit_ctx* ctx, const uint64_t* const* d_slices, uint32_t n_slices, const uint64_t* d_validity,
                           const uint64_t* d_filter, uint64_t n_rows, int type, int64_t base, int mode, uint64_t k, double q,
                           int64_t* d_out) {
@@ -1225,6 +1271,8 @@ struct cubit_table {
     uint32_t last_narrowed = 0;  // K0 leaves the last plan built only at the rows a mask kept
     std::vector<int32_t> last_narrow_cols;  // columns of the last plan's K0 leaves, in build order
     bool last_sum_packed = false;  // the last sum_product read a from its BITPACKING segments
+    bool last_sum_slices = false;  // the last cubit_table_sum_product read both operands' slices …
+    uint32_t last_sum_launches = 0;  // … in this many launches of the slice kernel
     bool last_agg_slices = false;  // the last cubit_table_aggregate read the column's slices
     bool last_sel_slices = false;  // the last cubit_table_select read the column's slices
     uint32_t last_sel_passes = 0;  // its passes over the slices or the probed values
@@ -5359,9 +5407,19 @@ extern "C" int cubit_table_sum_product(cubit_table* t, const cubit_filter_node* 
     if (ait == t->cols.end() || bit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column not registered");
     if (ait->second.type != CUBIT_TYPE_INT64 || bit->second.type != CUBIT_TYPE_INT64)
         return fail(CUBIT_ERR_UNSUPPORTED, "sum_product needs INT64 (DECIMAL storage) columns");
-    if (int rc = set_device(t->ctx)) return rc;
+    // the slice path needs both operands' slices usable (bind_slices: no update record of either
+    // visible); it writes no row ids, so no tile directory (the fallback's scan resets it below)
+    SlicePlan pa, pb;
+    if (int rc = forced_path(flags & CUBIT_SUM_FROM_SLICES, flags & CUBIT_SUM_FROM_COLUMN, pa)) return rc;
+    pb.force_slices = pa.force_slices;
+    pb.force_column = pa.force_column;
+    const int ruling[2] = {col_a, col_b};
+    if (int rc = bind_slices(t, txn, col_a, ait->second, ruling, 2, pa)) return rc;
+    if (int rc = bind_slices(t, txn, col_b, bit->second, ruling, 2, pb)) return rc;
+    const bool usable = pa.sx && pb.sx;
+    t->last_sum_slices = false;
+    t->last_sum_launches = 0;
     cubit_ctx* ctx = t->ctx;
-    ctx->last_tiles = 0;  // writes no row ids, so no tile directory (the fallback's scan resets it below)
     uint64_t* count = d_count ? d_count : t->dummy_count;
     if (t->n_rows == 0) {  // empty partition: sum 0 over 0 rows
         HIP_CHECK(hipMemsetAsync(d_out, 0, 2 * sizeof(int64_t), ctx->stream));
@@ -5392,6 +5450,9 @@ extern "C" int cubit_table_sum_product(cubit_table* t, const cubit_filter_node* 
         ctx->last_tiles = 0;  // the directory described ids in scratch, not a caller's buffer
         return CUBIT_OK;
     }
+    uint64_t est_rows = t->n_rows;  // estimated only when the path rule will be asked
+    if (usable && !pa.force_slices && !pa.force_column)
+        if (int rc = cubit_table_estimate_rows(t, nodes, n_nodes, &est_rows)) return rc;
     Emitter em;
     bool empty = false;
     std::vector<uint32_t> live;
@@ -5405,6 +5466,41 @@ extern "C" int cubit_table_sum_product(cubit_table* t, const cubit_filter_node* 
         return CUBIT_OK;
     }
     t->last_live = live.empty() ? t->last_zones : (uint32_t)live.size();
+    std::vector<int64_t> vals;
+    std::vector<const uint64_t*> dl;
+    const bool decode_b = !(flags & CUBIT_SUM_GATHER_B) && decodable_values(t, nodes, n_nodes, col_b, vals, dl);
+    if (usable) {
+        // sum_product_from_slices (cubit_program.hpp) chooses between the slices of both operands and
+        // the fused gather below
+        const uint32_t n_a = pa.bits(), n_b = pb.bits();
+        const uint64_t live_rows = std::min<uint64_t>(t->n_rows, (uint64_t)t->last_live * kZoneRows);
+        if (sum_product_from_slices(pa.force_slices, pa.force_column, true, n_a, n_b, em.prog.n_leaves,
+                                    ait->second.validity != nullptr, bit->second.validity != nullptr, live_rows, t->n_rows,
+                                    est_rows, decode_b ? (int)dl.size() : -1)) {
+            const bool a_outer = n_a >= n_b;
+            const SlicePlan &po = a_outer ? pa : pb, &pi = a_outer ? pb : pa;
+            SliceProductArgs g{};
+            g.outer = slice_set(*po.sx);
+            g.inner = slice_set(*pi.sx);
+            g.n_outer = po.bits();
+            g.n_inner = pi.bits();
+            g.valid_a = ait->second.validity;
+            g.valid_b = bit->second.validity;
+            g.workspace = ctx->agg;
+            EvalArgs a;
+            if (int rc = tile_eval_args(ctx, em.prog, t->n_rows, t->row_base, kAggTileWords, live, a)) return rc;
+            hipEvent_t e0, e1;
+            if (int rc = timing_events(ctx, e0, e1)) return rc;
+            HIP_CHECK(launch_eval_slice_sum_product(a, g, po.sx->vmin, pi.sx->vmin, ctx->n_cus, d_out, 2, count, ctx->stream,
+                                                    e0, e1));
+            t->last_sum_slices = true;
+            t->last_sum_launches = 1;
+            t->last_sliced += 2;
+            t->last_sum_packed = false;
+            t->last_decoded = 0;
+            return CUBIT_OK;
+        }
+    }
     SumArgs sa{};
     sa.a = static_cast<const int64_t*>(ait->second.data);
     sa.a_valid = ait->second.validity;
@@ -5418,9 +5514,7 @@ extern "C" int cubit_table_sum_product(cubit_table* t, const cubit_filter_node* 
         t->last_sum_packed = true;
     }
     sa.partials = ctx->partials;
-    std::vector<int64_t> vals;
-    std::vector<const uint64_t*> dl;
-    if (!(flags & CUBIT_SUM_GATHER_B) && decodable_values(t, nodes, n_nodes, col_b, vals, dl)) {
+    if (decode_b) {
         sa.b = nullptr;
         sa.v0 = vals[0];
         sa.n_decode = (uint32_t)dl.size();
@@ -5502,6 +5596,14 @@ extern "C" int cubit_table_aggregate(cubit_table* t, const cubit_filter_node* no
     if (int rc = probe_impl(t, col, txn, s.ids, s.count, s.cap, s.values_of(0), s.valid_of(0))) return rc;
     HIP_CHECK(launch_aggregate_arrays(s.values_of(0), s.valid_of(0), s.count, s.cap, ops & kOps, c.type, ctx->agg, d_out,
                                       ctx->stream));
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_last_sum_product(cubit_table* t, int* from_slices, uint32_t* n_launches) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    if (from_slices) *from_slices = t->last_sum_slices ? 1 : 0;
+    if (n_launches) *n_launches = t->last_sum_launches;
     return CUBIT_OK;
 }
 
@@ -5712,6 +5814,74 @@ int ensure_grouped(cubit_ctx* ctx) {
     return CUBIT_OK;
 }
 
+// The column path's group side: each group column probed into the scratch's columns first, first + 1
+// (visible updates applied), and its slot keys staged to the device.
+int probe_group_columns(cubit_table* t, const cubit_txn* txn, const GroupCol (&gc)[CUBIT_AGG_MAX_GROUP_COLS],
+                        uint32_t n_group_cols, uint32_t n2, const ColumnScratch& cs, uint32_t first, GroupColArgs& ga) {
+    cubit_ctx* ctx = t->ctx;
+    ga.n_cols = n_group_cols;
+    ga.n2 = n2;
+    if (ctx->gkeys_pending) {  // the previous keys' copy must be done before the staging is reused
+        HIP_CHECK(hipEventSynchronize(ctx->gkeys_ev));
+        ctx->gkeys_pending = false;
+    }
+    for (uint32_t k = 0; k < n_group_cols; ++k) {
+        if (int rc = probe_impl(t, gc[k].col, txn, cs.ids, cs.count, cs.cap, cs.values_of(first + k), cs.valid_of(first + k)))
+            return rc;
+        const GroupSlots& s = gc[k].slots;
+        std::copy(s.keys.begin(), s.keys.end(), ctx->gkeys_host + (size_t)k * CUBIT_AGG_MAX_GROUPS);
+        ga.v[k] = cs.values_of(first + k);
+        ga.valid[k] = cs.valid_of(first + k);
+        ga.keys[k] = ctx->gkeys_dev + (size_t)k * CUBIT_AGG_MAX_GROUPS;
+        ga.n_keys[k] = (uint32_t)s.keys.size();
+        ga.null_slot[k] = s.has_null ? (int32_t)s.keys.size() : -1;
+        ga.type[k] = gc[k].c->type;
+    }
+    HIP_CHECK(hipMemcpyAsync(ctx->gkeys_dev, ctx->gkeys_host,
+                             (size_t)CUBIT_AGG_MAX_GROUP_COLS * CUBIT_AGG_MAX_GROUPS * sizeof(int64_t),
+                             hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipEventRecord(ctx->gkeys_ev, ctx->stream));
+    ctx->gkeys_pending = true;
+    return CUBIT_OK;
+}
+
+// The launch arguments of one rectangle of groups (GroupBatch) over the leaves of the two lists
+void fill_group_batch(const GroupBatch& b, const std::vector<GroupLeaf>& la, const std::vector<GroupLeaf>& lb, bool two,
+                      bool swapped, uint32_t n2, GroupAggArgs& q) {
+    q.n1 = b.na;
+    q.n2 = b.nb;
+    for (uint32_t j = 0; j < kGroupBatchSum; ++j) q.group[j] = kNoGroup;
+    for (uint32_t x = 0; x < b.na; ++x) {
+        q.e1[x] = la[b.a0 + x].bv;
+        q.neg1 |= la[b.a0 + x].neg ? 1u << x : 0u;
+    }
+    for (uint32_t y = 0; y < b.nb; ++y) {
+        q.e2[y] = lb[b.b0 + y].bv;
+        q.neg2 |= lb[b.b0 + y].neg ? 1u << y : 0u;
+    }
+    for (uint32_t x = 0; x < b.na; ++x) {
+        if (!two) {
+            q.group[x] = la[b.a0 + x].slot;
+            continue;
+        }
+        for (uint32_t y = 0; y < b.nb; ++y) {
+            const uint32_t sa = la[b.a0 + x].slot, sb = lb[b.b0 + y].slot;
+            q.group[2 * x + y] = swapped ? group_index(sb, sa, n2) : group_index(sa, sb, n2);
+        }
+    }
+}
+
+// the slots that have a bitvector: a key's index leaf, and the NULL slot of a nullable column
+void group_leaves(const GroupCol (&gc)[CUBIT_AGG_MAX_GROUP_COLS], uint32_t n_group_cols,
+                  std::vector<GroupLeaf> (&leaves)[CUBIT_AGG_MAX_GROUP_COLS]) {
+    for (uint32_t k = 0; k < n_group_cols; ++k) {
+        const GroupSlots& s = gc[k].slots;
+        for (uint32_t i = 0; i < s.keys.size(); ++i)
+            if (s.leaf[i] >= 0) leaves[k].push_back({gc[k].ix->bvs[(size_t)s.leaf[i]], false, i});
+        if (s.has_null && gc[k].c->validity) leaves[k].push_back({gc[k].c->validity, true, (uint32_t)s.keys.size()});
+    }
+}
+
 }  // namespace
 
 extern "C" int cubit_table_aggregate_groups(cubit_table* t, const int* group_cols, uint32_t n_group_cols, int64_t* keys,
@@ -5775,14 +5945,8 @@ extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_
     if (p.no_rows) return CUBIT_OK;
     if (int rc = ensure_grouped(ctx)) return rc;
 
-    // the slots that have a bitvector: a key's index leaf, and the NULL slot of a nullable column
     std::vector<GroupLeaf> leaves[CUBIT_AGG_MAX_GROUP_COLS];
-    for (uint32_t k = 0; k < n_group_cols; ++k) {
-        const GroupSlots& s = gc[k].slots;
-        for (uint32_t i = 0; i < s.keys.size(); ++i)
-            if (s.leaf[i] >= 0) leaves[k].push_back({gc[k].ix->bvs[(size_t)s.leaf[i]], false, i});
-        if (s.has_null && gc[k].c->validity) leaves[k].push_back({gc[k].c->validity, true, (uint32_t)s.keys.size()});
-    }
+    group_leaves(gc, n_group_cols, leaves);
     const bool two = n_group_cols > 1;
     const bool minmax = (ops & (CUBIT_AGG_MIN | CUBIT_AGG_MAX)) != 0;
     const uint32_t row_bits = p.bits() + p.em.prog.n_leaves + (c.validity ? 1u : 0u);
@@ -5806,27 +5970,7 @@ extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_
         for (const GroupBatch& b : batches) {
             GroupAggArgs q{};
             q.partials = ctx->gagg;
-            q.n1 = b.na;
-            q.n2 = b.nb;
-            for (uint32_t j = 0; j < kGroupBatchSum; ++j) q.group[j] = kNoGroup;
-            for (uint32_t x = 0; x < b.na; ++x) {
-                q.e1[x] = la[b.a0 + x].bv;
-                q.neg1 |= la[b.a0 + x].neg ? 1u << x : 0u;
-            }
-            for (uint32_t y = 0; y < b.nb; ++y) {
-                q.e2[y] = lb[b.b0 + y].bv;
-                q.neg2 |= lb[b.b0 + y].neg ? 1u << y : 0u;
-            }
-            for (uint32_t x = 0; x < b.na; ++x) {
-                if (!two) {
-                    q.group[x] = la[b.a0 + x].slot;
-                    continue;
-                }
-                for (uint32_t y = 0; y < b.nb; ++y) {
-                    const uint32_t sa = la[b.a0 + x].slot, sb = lb[b.b0 + y].slot;
-                    q.group[2 * x + y] = swapped ? group_index(sb, sa, n2) : group_index(sa, sb, n2);
-                }
-            }
+            fill_group_batch(b, la, lb, two, swapped, n2, q);
             hipEvent_t e0, e1;
             if (int rc = timing_events(ctx, e0, e1)) return rc;
             HIP_CHECK(launch_eval_slice_aggregate_grouped(a, g, q, ops & kOps, c.type, p.sx->vmin, ctx->n_cus, d_out,
@@ -5842,29 +5986,7 @@ extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_
     if (int rc = decode_to_scratch(t, p, 1 + n_group_cols, cs)) return rc;
     if (int rc = probe_impl(t, col, txn, cs.ids, cs.count, cs.cap, cs.values_of(0), cs.valid_of(0))) return rc;
     GroupColArgs ga{};
-    ga.n_cols = n_group_cols;
-    ga.n2 = n2;
-    if (ctx->gkeys_pending) {  // the previous keys' copy must be done before the staging is reused
-        HIP_CHECK(hipEventSynchronize(ctx->gkeys_ev));
-        ctx->gkeys_pending = false;
-    }
-    for (uint32_t k = 0; k < n_group_cols; ++k) {
-        if (int rc = probe_impl(t, gc[k].col, txn, cs.ids, cs.count, cs.cap, cs.values_of(1 + k), cs.valid_of(1 + k)))
-            return rc;
-        const GroupSlots& s = gc[k].slots;
-        std::copy(s.keys.begin(), s.keys.end(), ctx->gkeys_host + (size_t)k * CUBIT_AGG_MAX_GROUPS);
-        ga.v[k] = cs.values_of(1 + k);
-        ga.valid[k] = cs.valid_of(1 + k);
-        ga.keys[k] = ctx->gkeys_dev + (size_t)k * CUBIT_AGG_MAX_GROUPS;
-        ga.n_keys[k] = (uint32_t)s.keys.size();
-        ga.null_slot[k] = s.has_null ? (int32_t)s.keys.size() : -1;
-        ga.type[k] = gc[k].c->type;
-    }
-    HIP_CHECK(hipMemcpyAsync(ctx->gkeys_dev, ctx->gkeys_host,
-                             (size_t)CUBIT_AGG_MAX_GROUP_COLS * CUBIT_AGG_MAX_GROUPS * sizeof(int64_t),
-                             hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(hipEventRecord(ctx->gkeys_ev, ctx->stream));
-    ctx->gkeys_pending = true;
+    if (int rc = probe_group_columns(t, txn, gc, n_group_cols, n2, cs, 1, ga)) return rc;
     HIP_CHECK(launch_aggregate_arrays_grouped(cs.values_of(0), cs.valid_of(0), ga, n_groups, cs.count, cs.cap, ops & kOps,
                                               c.type, ctx->gagg, d_out, ctx->stream));
     return CUBIT_OK;
@@ -5876,6 +5998,101 @@ extern "C" int cubit_table_last_grouped(cubit_table* t, int* from_slices, uint32
     if (from_slices) *from_slices = t->last_grouped_slices ? 1 : 0;
     if (n_groups) *n_groups = t->last_grouped_groups;
     if (n_launches) *n_launches = t->last_grouped_launches;
+    return CUBIT_OK;
+}
+
+// cubit_table_sum_product per group: cubit_table_aggregate_grouped's structure with two value columns.
+// sum_product_grouped_from_slices (cubit_program.hpp) chooses between the fused kernel over both
+// operands' slices and scan + probe (a, b, the group columns) + the grouped reduction.
+extern "C" int cubit_table_sum_product_grouped(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_nodes,
+                                               const cubit_txn* txn, int col_a, int col_b, const int* group_cols,
+                                               uint32_t n_group_cols, uint32_t flags, int64_t* d_out, uint32_t cap_groups) {
+    if (!t || !d_out || !group_cols) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    if (n_nodes && !nodes) return fail(CUBIT_ERR_INVALID, "nodes is null");
+    if (flags & ~(CUBIT_SUM_FROM_SLICES | CUBIT_SUM_FROM_COLUMN | CUBIT_SUM_NO_ZONEMAP))
+        return fail(CUBIT_ERR_INVALID, "flags %u", flags);
+    SlicePlan p, pb;
+    if (int rc = forced_path(flags & CUBIT_SUM_FROM_SLICES, flags & CUBIT_SUM_FROM_COLUMN, p)) return rc;
+    pb.force_slices = p.force_slices;
+    pb.force_column = p.force_column;
+    auto ait = t->cols.find(col_a), bit = t->cols.find(col_b);
+    if (ait == t->cols.end() || bit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column not registered");
+    const Column &ca = ait->second, &cb = bit->second;
+    if (ca.type != CUBIT_TYPE_INT64 || cb.type != CUBIT_TYPE_INT64)
+        return fail(CUBIT_ERR_UNSUPPORTED, "sum_product needs INT64 (DECIMAL storage) columns");
+    GroupCol gc[CUBIT_AGG_MAX_GROUP_COLS];
+    uint32_t n1 = 0, n2 = 1;
+    if (int rc = group_columns(t, group_cols, n_group_cols, gc, &n1, &n2)) return rc;
+    const uint32_t n_groups = n1 * n2;
+    if (cap_groups < n_groups) return fail(CUBIT_ERR_CAPACITY, "%u groups, room for %u", n_groups, cap_groups);
+    // an update record of either operand or of a group column rules the slices out
+    int ruling[2 + CUBIT_AGG_MAX_GROUP_COLS] = {col_a, col_b};
+    for (uint32_t k = 0; k < n_group_cols; ++k) ruling[2 + k] = gc[k].col;
+    if (int rc = bind_slices(t, txn, col_a, ca, ruling, 2 + n_group_cols, p)) return rc;
+    if (int rc = bind_slices(t, txn, col_b, cb, ruling, 2 + n_group_cols, pb)) return rc;
+    const Index* sxa = p.sx;
+    if (!pb.sx) p.sx = nullptr;  // usable: both operands' slices
+    const bool usable = p.sx != nullptr;
+    cubit_ctx* ctx = t->ctx;
+    t->last_sum_slices = false;
+    t->last_sum_launches = 0;
+    if (n_groups == 0) return CUBIT_OK;
+    // every group starts as four zeros: the kernels write the groups that reach them
+    HIP_CHECK(hipMemsetAsync(d_out, 0, (size_t)n_groups * 4 * sizeof(int64_t), ctx->stream));
+    if (int rc = plan_slice_query(t, nodes, n_nodes, txn, !(flags & CUBIT_SUM_NO_ZONEMAP), p)) return rc;
+    if (p.no_rows) return CUBIT_OK;
+    if (int rc = ensure_grouped(ctx)) return rc;
+
+    std::vector<GroupLeaf> leaves[CUBIT_AGG_MAX_GROUP_COLS];
+    group_leaves(gc, n_group_cols, leaves);
+    const bool two = n_group_cols > 1;
+    const uint32_t n_a = usable ? (uint32_t)sxa->bvs.size() : 0, n_b = usable ? pb.bits() : 0;
+    const uint32_t row_bits = product_slice_bits(n_a, n_b, p.em.prog.n_leaves, ca.validity != nullptr, cb.validity != nullptr);
+    bool swapped = false;
+    const std::vector<GroupBatch> batches = split_group_batches(
+        (uint32_t)leaves[0].size(), two ? (uint32_t)leaves[1].size() : 0u, two, kProductGroupBatch, row_bits, &swapped);
+    uint64_t elem_bytes[2 + CUBIT_AGG_MAX_GROUP_COLS] = {8, 8, 0, 0};
+    for (uint32_t k = 0; k < n_group_cols; ++k) elem_bytes[2 + k] = type_is32(gc[k].c->type) ? 4 : 8;
+    if (sum_product_grouped_from_slices(p.force_slices, p.force_column, usable, n_a, n_b,
+                                        batches.empty() ? row_bits : group_batches_bits(batches, row_bits),
+                                        p.em.prog.n_leaves, p.live_rows, t->n_rows, p.est_rows, elem_bytes,
+                                        2 + n_group_cols)) {
+        const bool a_outer = n_a >= n_b;
+        const Index &so = a_outer ? *sxa : *pb.sx, &si = a_outer ? *pb.sx : *sxa;
+        SliceProductArgs g{};
+        g.outer = slice_set(so);
+        g.inner = slice_set(si);
+        g.n_outer = (uint32_t)so.bvs.size();
+        g.n_inner = (uint32_t)si.bvs.size();
+        g.valid_a = ca.validity;
+        g.valid_b = cb.validity;
+        EvalArgs a;  // (the kernel counts each group's rows in its partials and takes no ticket)
+        if (int rc = tile_eval_args(ctx, p.em.prog, t->n_rows, t->row_base, kAggTileWords, p.live, a)) return rc;
+        const std::vector<GroupLeaf>& la = leaves[swapped ? 1 : 0];
+        const std::vector<GroupLeaf>& lb = leaves[swapped ? 0 : 1];
+        for (const GroupBatch& b : batches) {
+            GroupAggArgs q{};
+            q.partials = ctx->gagg;
+            fill_group_batch(b, la, lb, two, swapped, n2, q);
+            hipEvent_t e0, e1;
+            if (int rc = timing_events(ctx, e0, e1)) return rc;
+            HIP_CHECK(launch_eval_slice_sum_product_grouped(a, g, q, so.vmin, si.vmin, ctx->n_cus, d_out, ctx->stream, e0, e1));
+            t->last_sum_launches++;
+        }
+        t->last_sum_slices = true;
+        t->last_sliced += 2;
+        return CUBIT_OK;
+    }
+    // the column path: both operands and the group columns are probed
+    ColumnScratch cs;
+    if (int rc = decode_to_scratch(t, p, 2 + n_group_cols, cs)) return rc;
+    if (int rc = probe_impl(t, col_a, txn, cs.ids, cs.count, cs.cap, cs.values_of(0), cs.valid_of(0))) return rc;
+    if (int rc = probe_impl(t, col_b, txn, cs.ids, cs.count, cs.cap, cs.values_of(1), cs.valid_of(1))) return rc;
+    GroupColArgs ga{};
+    if (int rc = probe_group_columns(t, txn, gc, n_group_cols, n2, cs, 2, ga)) return rc;
+    HIP_CHECK(launch_sum_product_arrays_grouped(cs.values_of(0), cs.valid_of(0), cs.values_of(1), cs.valid_of(1), ga, n_groups,
+                                                cs.count, cs.cap, ctx->gagg, d_out, ctx->stream));
     return CUBIT_OK;
 }
 

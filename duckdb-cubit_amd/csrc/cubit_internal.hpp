@@ -248,6 +248,26 @@ hipError_t launch_eval_slice_aggregate(EvalArgs a, const SliceAggArgs& g, uint32
 // (bit i, null = all valid), i < min(*d_count, max_n)
 hipError_t launch_aggregate_arrays(const int64_t* x, const uint64_t* valid, const uint64_t* d_count, uint64_t max_n,
                                    uint32_t ops, int type, int64_t* workspace, int64_t* out, hipStream_t stream);
+// Σ a·b over a program's rows from the slices of both columns (eval_slice_sum_product). `outer` is
+// the operand with at least as many slices as `inner` (the sum is symmetric, so either column may be
+// either). The kernel leaves kProductPartial int64 per workgroup in the aggregate workspace —
+// {cross lo, hi, Σ outer offsets lo, hi, Σ inner offsets lo, hi, valid rows} — and one finishing wave
+// combines them (slice_product_combine, cubit_program.hpp) into out[0..1] = {sum_lo, sum_hi}, with
+// out_slots = 4 also out[2..3] = {count_valid, count_rows}; count_out (optional) gets count_rows too.
+constexpr int kProductPartial = 7;
+constexpr unsigned kProductMaxGrid = (unsigned)((uint64_t)kAggPartial * kAggMaxGrid / kProductPartial);
+struct SliceProductArgs {
+    SliceSet outer, inner;
+    uint32_t n_outer, n_inner;
+    // the operands' validities: null = every row valid; read only below ceil(n_rows / 64) words
+    const uint64_t* valid_a;
+    const uint64_t* valid_b;
+    int64_t* workspace;  // kAggWorkspace int64
+};
+// a as launch_eval_slice_aggregate's (a.count is set by the launcher)
+hipError_t launch_eval_slice_sum_product(EvalArgs a, const SliceProductArgs& g, int64_t base_outer, int64_t base_inner,
+                                         int n_cus, int64_t* out, int out_slots, uint64_t* count_out, hipStream_t stream,
+                                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // Selection by rank (cubit_table_select): a radix select over the column's slices (eval_slice_select,
 // slice_select_narrow: kSelectChunk slices per pass) or over probed values (select_arrays_kernel:
 // kSelectArrayBits bits per pass), one workgroup after each pass summing and walking the histogram
@@ -333,6 +353,22 @@ struct GroupColArgs {
 hipError_t launch_aggregate_arrays_grouped(const int64_t* x, const uint64_t* valid, const GroupColArgs& gc,
                                            uint32_t n_groups, const uint64_t* d_count, uint64_t max_n, uint32_t ops,
                                            int type, int64_t* partials, int64_t* out, hipStream_t stream);
+// Σ a·b per group (cubit_table_sum_product_grouped). Either kernel leaves kProductGroupPartial int64
+// per group and workgroup in `partials`, group-major — the ungrouped seven words, then the rows — and
+// one finishing wave per group writes out[4·group …] = {sum_lo, sum_hi, count_valid, count_rows}.
+// The slice kernel takes q as launch_eval_slice_aggregate_grouped does, q.n1 ≤ kProductGroupBatch with
+// one group column, half that with two; the grouped workspace (kGroupWorkspace) holds both paths'.
+constexpr int kProductGroupPartial = 8;
+static_assert((uint64_t)kProductGroupPartial * kProductGroupBatch * kAggMaxGrid <= kGroupWorkspace, "the slice path's partials fit");
+constexpr unsigned kProductColGrid = (unsigned)(kGroupWorkspace / ((uint64_t)kProductGroupPartial * CUBIT_AGG_MAX_GROUPS));
+hipError_t launch_eval_slice_sum_product_grouped(const EvalArgs& a, const SliceProductArgs& g, const GroupAggArgs& q,
+                                                 int64_t base_outer, int64_t base_inner, int n_cus, int64_t* out,
+                                                 hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// the column path's reduction: xa / xb the probed operands (0 at NULL rows) with their validity words
+// (null: all valid), gc as launch_aggregate_arrays_grouped's
+hipError_t launch_sum_product_arrays_grouped(const int64_t* xa, const uint64_t* va, const int64_t* xb, const uint64_t* vb,
+                                             const GroupColArgs& gc, uint32_t n_groups, const uint64_t* d_count,
+                                             uint64_t max_n, int64_t* partials, int64_t* out, hipStream_t stream);
 // after a merge: every 64-row word holding one of the m merged rows (ascending) sliced again from
 // the column as it stands
 hipError_t launch_bitslice_reslice(const int64_t* rows, uint64_t m, const void* col, int type, const uint64_t* validity,

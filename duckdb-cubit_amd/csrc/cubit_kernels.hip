@@ -2533,6 +2533,171 @@ __global__ __launch_bounds__(64) void aggregate_finish_kernel(const int64_t* __r
     }
 }
 
+// Sum of a product: Σ a·b over the rows a program keeps, from the two columns' slices alone
+// (cubit_program.hpp has the arithmetic; Rinfret et al. 2001). The tile walk, the program and the live
+// tiles are eval_slice_aggregate's. Per pair of words V = F ∧ valid_a ∧ valid_b; a group of up to
+// kProductInner slices of the inner operand (the one with fewer slices) is loaded and kept as
+// M_j = V ∧ B_j, and the outer operand's slices stream past them from the top down in chunks of
+// kProductChunk loaded before use (16-byte non-temporal loads, as agg_chunk). Per chunk and per j a
+// Horner popcount over the chunk gives local_j ≤ 128·(2^8 - 1); Σ_j local_j·2^j < 2^23 goes to the
+// thread's 128-bit cross accumulator with one shifted add. Σ of the outer offsets accumulates from
+// popc(V ∧ A_i) in the first pass, Σ of the inner offsets from popc(M_j). An inner operand wider
+// than kProductInner takes further groups, each streaming the outer slices again. The top chunk may
+// reach above the outer slices, and a group above the inner ones: a slice that does not exist reads as
+// zero. A pair whose V is zero across the wave loads nothing more (a wave-uniform branch).
+// Traffic: (K + validities + n_in + n_out·passes)·n/8 bytes over the live zones, nothing written;
+// n_in·n_out AND + popcount pairs per 64 rows.
+constexpr int kProductChunk = 8;
+// a partial: {cross lo, hi, Σ outer offsets lo, hi, Σ inner offsets lo, hi, valid rows}; exact adds,
+// so any order of merges gives the same
+__device__ __forceinline__ void product_merge(uint64_t* into, const uint64_t* from) {
+#pragma unroll
+    for (int k = 0; k < 6; k += 2) {
+        const U128 s = u128_add(U128{into[k], into[k + 1]}, U128{from[k], from[k + 1]});
+        into[k] = s.lo;
+        into[k + 1] = s.hi;
+    }
+    into[6] += from[6];
+}
+__device__ __forceinline__ void product_wave_reduce(uint64_t (&part)[kProductPartial]) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        uint64_t o[kProductPartial];
+#pragma unroll
+        for (int k = 0; k < kProductPartial; ++k) o[k] = __shfl_xor(part[k], d, 64);
+        product_merge(part, o);
+    }
+}
+
+template <int K, int FORM>
+__global__ __launch_bounds__(512, 4) void eval_slice_sum_product(EvalArgs a, SliceProductArgs g) {
+    constexpr int THREADS = 512, PAIRS = 2, NW = 4;
+    constexpr uint64_t TILE_WORDS = (uint64_t)THREADS * NW;
+    static_assert(TILE_WORDS == kAggTileWords, "a tile is one zone");
+    static_assert(PAIRS == 2, "the pair loop selects between two pairs");
+    constexpr int NWAVES = THREADS / 64;
+    constexpr int NI = (int)kProductInner, NC = kProductChunk;
+    static_assert(NI <= 8 && NC <= 8, "Σ_j local_j·2^j stays inside 32 bits");
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    U128 cross{0, 0}, s_out{0, 0}, s_in{0, 0};
+    uint64_t c_valid = 0, c_rows = 0;
+    const int n_out = (int)g.n_outer, n_in = (int)g.n_inner;
+    const int top0 = (n_out + NC - 1) / NC * NC - 1;  // the top chunk's highest slot (-1: no outer slice)
+    const uint32_t n_idx = a.num_tiles;
+    for (uint32_t i = blockIdx.x; i < n_idx; i += gridDim.x) {
+        const uint64_t tile_word0 = (uint64_t)tile_at(a, i) * TILE_WORDS;
+        uint64_t r[NW];
+        eval_tile<K, FORM, NW, THREADS>(a, tile_word0, t, r);
+        const bool whole = tile_word0 + TILE_WORDS <= a.n_words;
+        // one pair at a time (p is uniform, so the selects are scalar): both pairs' masks and chunks
+        // in flight would not fit the register file
+#pragma unroll 1
+        for (int p = 0; p < PAIRS; ++p) {
+            u64x2 v;
+            v.x = p ? r[2] : r[0];
+            v.y = p ? r[3] : r[1];
+            c_rows += (uint64_t)(__popcll(v.x) + __popcll(v.y));
+            if (__ballot((v.x | v.y) != 0) == 0) continue;  // no qualifying row in the wave's 128 words
+            if (g.valid_a) v &= load_pair<THREADS>(g.valid_a, false, whole, tile_word0, p, t, a.n_words);
+            if (g.valid_b) v &= load_pair<THREADS>(g.valid_b, false, whole, tile_word0, p, t, a.n_words);
+            c_valid += (uint64_t)(__popcll(v.x) + __popcll(v.y));
+            if (__ballot((v.x | v.y) != 0) == 0) continue;
+            const uint64_t pi = (tile_word0 >> 1) + (uint64_t)(p * THREADS + t);
+            int g0 = 0;
+            do {
+                const int cnt = n_in - g0 < NI ? n_in - g0 : NI;
+                u64x2 m[NI];
+#pragma unroll
+                for (int j = 0; j < NI; ++j) {
+                    m[j] = u64x2{0ull, 0ull};
+                    if (j < cnt) m[j] = v & __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(g.inner.s[g0 + j]) + pi);
+                }
+                uint32_t li = 0;
+#pragma unroll
+                for (int j = 0; j < NI; ++j) li += (uint32_t)(__popcll(m[j].x) + __popcll(m[j].y)) << j;
+                s_in = u128_add(s_in, u128_shl_wide(li, (uint32_t)g0));
+#pragma unroll 1
+                for (int top = top0; top >= 0; top -= NC) {
+                    u64x2 w[NC];
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        w[c] = u64x2{0ull, 0ull};
+                        if (top - c < n_out)
+                            w[c] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(g.outer.s[top - c]) + pi);
+                    }
+                    const uint32_t low = (uint32_t)(top - NC + 1);
+                    if (g0 == 0) {
+                        uint32_t lo = 0;
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) lo = (lo << 1) + (uint32_t)(__popcll(v.x & w[c].x) + __popcll(v.y & w[c].y));
+                        s_out = u128_add(s_out, u128_shl(lo, low));
+                    }
+                    uint32_t comb = 0;
+#pragma unroll
+                    for (int j = 0; j < NI; ++j) {
+                        if (j >= cnt) continue;  // uniform
+                        uint32_t l = 0;  // Horner from the chunk's top slice
+#pragma unroll
+                        for (int c = 0; c < NC; ++c)
+                            l = (l << 1) + (uint32_t)(__popcll(m[j].x & w[c].x) + __popcll(m[j].y & w[c].y));
+                        comb += l << j;
+                    }
+                    cross = u128_add(cross, u128_shl_wide(comb, low + (uint32_t)g0));
+                }
+                g0 += NI;
+            } while (g0 < n_in);
+        }
+    }
+    // wave, then workgroup
+    uint64_t part[kProductPartial] = {cross.lo, cross.hi, s_out.lo, s_out.hi, s_in.lo, s_in.hi, c_valid};
+    product_wave_reduce(part);
+    c_rows = wave_sum(c_rows);
+    __shared__ uint64_t s_part[NWAVES][kProductPartial + 1];
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < kProductPartial; ++k) s_part[wave][k] = part[k];
+        s_part[wave][kProductPartial] = c_rows;
+    }
+    __syncthreads();
+    if (t == 0) {
+        uint64_t rows = s_part[0][kProductPartial];
+        for (int w = 1; w < NWAVES; ++w) {
+            product_merge(s_part[0], s_part[w]);
+            rows += s_part[w][kProductPartial];
+        }
+        int64_t* o = g.workspace + (uint64_t)kProductPartial * blockIdx.x;
+#pragma unroll
+        for (int k = 0; k < kProductPartial; ++k) o[k] = (int64_t)s_part[0][k];
+        finish_ticket(a.ticket, a.count, rows);
+    }
+}
+
+// One wave combines the workgroups' partials and writes {sum_lo, sum_hi} (slice_product_combine),
+// with out_slots = 4 also {count_valid, count_rows}; count_out (optional) gets the rows as well.
+__global__ __launch_bounds__(64) void slice_product_finish_kernel(const int64_t* __restrict__ workspace, int nblocks,
+                                                                  int64_t base_outer, int64_t base_inner,
+                                                                  int64_t* __restrict__ out, int out_slots,
+                                                                  uint64_t* __restrict__ count_out) {
+    const int lane = threadIdx.x;
+    uint64_t part[kProductPartial] = {0, 0, 0, 0, 0, 0, 0};
+    for (int b = lane; b < nblocks; b += 64)
+        product_merge(part, reinterpret_cast<const uint64_t*>(workspace) + (uint64_t)kProductPartial * b);
+    product_wave_reduce(part);
+    if (lane == 0) {
+        int64_t r[2];
+        slice_product_combine(base_outer, base_inner, part[6], U128{part[0], part[1]}, U128{part[2], part[3]},
+                              U128{part[4], part[5]}, r);
+        const uint64_t rows = (uint64_t)workspace[(uint64_t)kAggPartial * kAggMaxGrid];
+        out[0] = r[0];
+        out[1] = r[1];
+        if (out_slots >= 4) {
+            out[2] = (int64_t)part[6];
+            out[3] = (int64_t)rows;
+        }
+        if (count_out) *count_out = rows;
+    }
+}
+
 // Select: the k-th smallest / largest value (or quantile_disc) of the column over the rows a program
 // keeps, from the slices alone — a radix select over the offsets, most significant slices first,
 // kSelectChunk slices per pass (cubit_program.hpp has the step logic, shared with the CPU).
@@ -3104,6 +3269,250 @@ __global__ __launch_bounds__(64) void aggregate_grouped_finish_kernel(const int6
         o[3] = r[3];
         o[4] = (int64_t)part.valid;
         o[5] = (int64_t)part.rows;
+    }
+}
+
+// GROUP BY for the sum of a product: eval_slice_sum_product's loop nest per group over a rectangle of
+// kProductGroupBatch groups, formed as eval_slice_aggregate_grouped forms them (m = F ∧ E1_a ∧ E2_b,
+// the NULL slot the complemented validity; rows counted, then ∧ valid_a ∧ valid_b). The inner group's
+// slices stay unmasked in registers; per chunk of kProductGroupChunk outer slices and per live group
+// the chunk is masked once (wq = m ∧ w) and every inner slice takes its Horner popcount over it. A
+// pair whose F is zero across the wave loads nothing more, one whose groups' valid rows are all zero
+// skips the slices, a group whose mask is zero across the wave skips its arithmetic (wave-uniform
+// branches). Partials are group-major, kProductGroupPartial words: the ungrouped seven, then the rows.
+// Traffic: (K + validities + n_in + n_out·passes + the launch's group leaves)·n/8 bytes per launch.
+constexpr int kProductGroupChunk = 4;
+__device__ __forceinline__ void product_merge_rows(uint64_t* into, const uint64_t* from) {
+    product_merge(into, from);
+    into[7] += from[7];
+}
+template <int K, int FORM, bool TWO>
+__global__ __launch_bounds__(512, 2) void eval_slice_sum_product_grouped(EvalArgs a, SliceProductArgs g, GroupAggArgs q) {
+    constexpr int THREADS = 512, PAIRS = 2, NW = 4;
+    constexpr uint64_t TILE_WORDS = (uint64_t)THREADS * NW;
+    static_assert(TILE_WORDS == kAggTileWords, "a tile is one zone");
+    static_assert(PAIRS == 2, "the pair loop selects between two pairs");
+    constexpr int NWAVES = THREADS / 64;
+    constexpr int NG = (int)kProductGroupBatch, NA = TWO ? NG / 2 : NG;
+    constexpr int NI = (int)kProductInner, NC = kProductGroupChunk;
+    static_assert(NG <= (int)kGroupBatchSum, "GroupAggArgs holds the batch");
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    U128 cross[NG], s_out[NG], s_in[NG];
+    uint64_t c_valid[NG], c_rows[NG];
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        cross[j] = s_out[j] = s_in[j] = U128{0, 0};
+        c_valid[j] = c_rows[j] = 0;
+    }
+    const int n_out = (int)g.n_outer, n_in = (int)g.n_inner;
+    const int top0 = (n_out + NC - 1) / NC * NC - 1;
+    const uint32_t n_idx = a.num_tiles;
+    for (uint32_t i = blockIdx.x; i < n_idx; i += gridDim.x) {
+        const uint64_t tile_word0 = (uint64_t)tile_at(a, i) * TILE_WORDS;
+        uint64_t r[NW];
+        eval_tile<K, FORM, NW, THREADS>(a, tile_word0, t, r);
+        const bool whole = tile_word0 + TILE_WORDS <= a.n_words;
+#pragma unroll 1
+        for (int p = 0; p < PAIRS; ++p) {
+            u64x2 f;
+            f.x = p ? r[2] : r[0];
+            f.y = p ? r[3] : r[1];
+            if (__ballot((f.x | f.y) != 0) == 0) continue;  // no qualifying row in the wave's 128 words
+            u64x2 m[NG];
+            if (TWO) {
+                u64x2 eb[2];
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    eb[b] = u64x2{0ull, 0ull};
+                    if ((uint32_t)b < q.n2)
+                        eb[b] = load_pair<THREADS>(q.e2[b], (q.neg2 >> b) & 1u, whole, tile_word0, p, t, a.n_words);
+                }
+#pragma unroll
+                for (int x = 0; x < NA; ++x) {
+                    u64x2 ea = {0ull, 0ull};
+                    if ((uint32_t)x < q.n1)
+                        ea = f & load_pair<THREADS>(q.e1[x], (q.neg1 >> x) & 1u, whole, tile_word0, p, t, a.n_words);
+                    m[2 * x] = ea & eb[0];
+                    m[2 * x + 1] = ea & eb[1];
+                }
+            } else {
+#pragma unroll
+                for (int x = 0; x < NA; ++x) {
+                    m[x] = u64x2{0ull, 0ull};
+                    if ((uint32_t)x < q.n1)
+                        m[x] = f & load_pair<THREADS>(q.e1[x], (q.neg1 >> x) & 1u, whole, tile_word0, p, t, a.n_words);
+                }
+            }
+            u64x2 vv = {~0ull, ~0ull};
+            if (g.valid_a) vv &= load_pair<THREADS>(g.valid_a, false, whole, tile_word0, p, t, a.n_words);
+            if (g.valid_b) vv &= load_pair<THREADS>(g.valid_b, false, whole, tile_word0, p, t, a.n_words);
+            uint32_t live = 0;
+#pragma unroll
+            for (int j = 0; j < NG; ++j) {
+                c_rows[j] += (uint64_t)(__popcll(m[j].x) + __popcll(m[j].y));
+                m[j] &= vv;
+                c_valid[j] += (uint64_t)(__popcll(m[j].x) + __popcll(m[j].y));
+                if (__ballot((m[j].x | m[j].y) != 0) != 0) live |= 1u << j;
+            }
+            if (live == 0) continue;
+            const uint64_t pi = (tile_word0 >> 1) + (uint64_t)(p * THREADS + t);
+            int g0 = 0;
+            do {
+                const int cnt = n_in - g0 < NI ? n_in - g0 : NI;
+                u64x2 b[NI];
+#pragma unroll
+                for (int j = 0; j < NI; ++j) {
+                    b[j] = u64x2{0ull, 0ull};
+                    if (j < cnt) b[j] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(g.inner.s[g0 + j]) + pi);
+                }
+#pragma unroll
+                for (int x = 0; x < NG; ++x) {
+                    if (!((live >> x) & 1u)) continue;
+                    uint32_t li = 0;
+#pragma unroll
+                    for (int j = 0; j < NI; ++j) li += (uint32_t)(__popcll(m[x].x & b[j].x) + __popcll(m[x].y & b[j].y)) << j;
+                    s_in[x] = u128_add(s_in[x], u128_shl_wide(li, (uint32_t)g0));
+                }
+#pragma unroll 1
+                for (int top = top0; top >= 0; top -= NC) {
+                    u64x2 w[NC];
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        w[c] = u64x2{0ull, 0ull};
+                        if (top - c < n_out)
+                            w[c] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(g.outer.s[top - c]) + pi);
+                    }
+                    const uint32_t low = (uint32_t)(top - NC + 1);
+#pragma unroll
+                    for (int x = 0; x < NG; ++x) {
+                        if (!((live >> x) & 1u)) continue;  // no valid row of this group in the wave's 128 words
+                        u64x2 wq[NC];
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) wq[c] = m[x] & w[c];
+                        if (g0 == 0) {
+                            uint32_t lo = 0;
+#pragma unroll
+                            for (int c = 0; c < NC; ++c) lo = (lo << 1) + (uint32_t)(__popcll(wq[c].x) + __popcll(wq[c].y));
+                            s_out[x] = u128_add(s_out[x], u128_shl(lo, low));
+                        }
+                        uint32_t comb = 0;
+#pragma unroll
+                        for (int j = 0; j < NI; ++j) {
+                            if (j >= cnt) continue;  // uniform
+                            uint32_t l = 0;
+#pragma unroll
+                            for (int c = 0; c < NC; ++c)
+                                l = (l << 1) + (uint32_t)(__popcll(b[j].x & wq[c].x) + __popcll(b[j].y & wq[c].y));
+                            comb += l << j;
+                        }
+                        cross[x] = u128_add(cross[x], u128_shl_wide(comb, low + (uint32_t)g0));
+                    }
+                }
+                g0 += NI;
+            } while (g0 < n_in);
+        }
+    }
+    // wave, then workgroup, per group
+    __shared__ uint64_t s_part[NWAVES][NG][kProductGroupPartial];
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        uint64_t part[kProductPartial] = {cross[j].lo, cross[j].hi, s_out[j].lo, s_out[j].hi,
+                                          s_in[j].lo,  s_in[j].hi,  c_valid[j]};
+        product_wave_reduce(part);
+        const uint64_t rows = wave_sum(c_rows[j]);
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < kProductPartial; ++k) s_part[wave][j][k] = part[k];
+            s_part[wave][j][7] = rows;
+        }
+    }
+    __syncthreads();
+    if (t < NG) {
+        for (int w = 1; w < NWAVES; ++w) product_merge_rows(s_part[0][t], s_part[w][t]);
+        int64_t* o = q.partials + ((uint64_t)t * gridDim.x + blockIdx.x) * kProductGroupPartial;
+#pragma unroll
+        for (int k = 0; k < kProductGroupPartial; ++k) o[k] = (int64_t)s_part[0][t][k];
+    }
+}
+
+// The column path per group: xa / xb = the probed values of qualifying row i (0 at NULL rows), va / vb
+// their validity (null: all valid), the group columns as aggregate_arrays_grouped_kernel's. Each valid
+// row's 128-bit product goes to its group in LDS as four 32-bit limbs, each added to a 64-bit sum
+// that cannot wrap below 2^32 rows a workgroup; Σ_k limb_k·2^(32k) modulo 2^128 is the exact
+// two's-complement sum. The partials are the grouped slice kernel's, the sum in the cross slots.
+__global__ __launch_bounds__(256) void sum_product_arrays_grouped_kernel(const int64_t* __restrict__ xa,
+                                                                         const uint64_t* __restrict__ va,
+                                                                         const int64_t* __restrict__ xb,
+                                                                         const uint64_t* __restrict__ vb,
+                                                                         GroupColArgs gc, uint32_t n_groups,
+                                                                         const uint64_t* __restrict__ d_count,
+                                                                         uint64_t max_n, int64_t* __restrict__ partials) {
+    // per group: {limb 0 … 3, valid rows, rows}
+    __shared__ unsigned long long s_acc[CUBIT_AGG_MAX_GROUPS][6];
+    const uint64_t n = min(*d_count, max_n);
+    for (uint32_t q = threadIdx.x; q < n_groups; q += blockDim.x) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s_acc[q][k] = 0ull;
+    }
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const int s1 = group_slot_of(gc, 0, i);
+        const int s2 = gc.n_cols > 1 ? group_slot_of(gc, 1, i) : 0;
+        if (s1 < 0 || s2 < 0) continue;
+        unsigned long long* acc = s_acc[(uint32_t)s1 * gc.n2 + (uint32_t)s2];
+        atomicAdd(&acc[5], 1ull);
+        if (va && !((va[i >> 6] >> (i & 63)) & 1ull)) continue;
+        if (vb && !((vb[i >> 6] >> (i & 63)) & 1ull)) continue;
+        atomicAdd(&acc[4], 1ull);
+        const unsigned __int128 pr = (unsigned __int128)((__int128)xa[i] * (__int128)xb[i]);
+        const uint64_t lo = (uint64_t)pr, hi = (uint64_t)(pr >> 64);
+        atomicAdd(&acc[0], (unsigned long long)(uint32_t)lo);
+        atomicAdd(&acc[1], (unsigned long long)(lo >> 32));
+        atomicAdd(&acc[2], (unsigned long long)(uint32_t)hi);
+        atomicAdd(&acc[3], (unsigned long long)(hi >> 32));
+    }
+    __syncthreads();
+    for (uint32_t q = threadIdx.x; q < n_groups; q += blockDim.x) {
+        U128 s{s_acc[q][0], s_acc[q][2]};
+        s = u128_add(s, U128{s_acc[q][1] << 32, s_acc[q][1] >> 32});
+        s.hi += s_acc[q][3] << 32;
+        int64_t* part = partials + ((uint64_t)q * gridDim.x + blockIdx.x) * kProductGroupPartial;
+        part[0] = (int64_t)s.lo;
+        part[1] = (int64_t)s.hi;
+        part[2] = part[3] = part[4] = part[5] = 0;
+        part[6] = (int64_t)s_acc[q][4];
+        part[7] = (int64_t)s_acc[q][5];
+    }
+}
+
+// One wave per group (slot) combines the workgroups' partials (slice_product_combine; the column
+// path passes zero bases and sums) and writes the group's four result slots {sum_lo, sum_hi,
+// count_valid, count_rows}: four zeros for a group without a qualifying row. group: as
+// aggregate_grouped_finish_kernel's.
+__global__ __launch_bounds__(64) void sum_product_grouped_finish_kernel(const int64_t* __restrict__ partials, int nblocks,
+                                                                        GroupAggArgs q, int identity, int64_t base_outer,
+                                                                        int64_t base_inner, int64_t* __restrict__ out) {
+    const int lane = threadIdx.x;
+    const uint32_t slot = blockIdx.x;
+    const uint32_t group = identity ? slot : q.group[slot < kGroupBatchSum ? slot : 0];
+    if (group == kNoGroup) return;
+    uint64_t part[kProductGroupPartial] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int b = lane; b < nblocks; b += 64)
+        product_merge_rows(part, reinterpret_cast<const uint64_t*>(partials) + ((uint64_t)slot * nblocks + b) * kProductGroupPartial);
+    uint64_t head[kProductPartial];
+#pragma unroll
+    for (int k = 0; k < kProductPartial; ++k) head[k] = part[k];
+    product_wave_reduce(head);
+    const uint64_t rows = wave_sum(part[7]);
+    if (lane == 0) {
+        int64_t r[2];
+        slice_product_combine(base_outer, base_inner, head[6], U128{head[0], head[1]}, U128{head[2], head[3]},
+                              U128{head[4], head[5]}, r);
+        int64_t* o = out + (uint64_t)group * 4;
+        o[0] = r[0];
+        o[1] = r[1];
+        o[2] = (int64_t)head[6];
+        o[3] = (int64_t)rows;
     }
 }
 
@@ -4877,6 +5286,25 @@ hipError_t launch_eval_slice_aggregate(EvalArgs a, const SliceAggArgs& g, uint32
     return hipGetLastError();
 }
 
+hipError_t launch_eval_slice_sum_product(EvalArgs a, const SliceProductArgs& g, int64_t base_outer, int64_t base_inner,
+                                         int n_cus, int64_t* out, int out_slots, uint64_t* count_out, hipStream_t stream,
+                                         hipEvent_t ev0, hipEvent_t ev1) {
+    if (g.n_outer > kMaxSlices || g.n_inner > g.n_outer || a.num_tiles == 0 || !g.workspace || !a.ticket)
+        return hipErrorInvalidValue;
+    a.count = agg_count_slot(g.workspace);
+    // two workgroups per CU, as the aggregate's; the workspace holds kProductMaxGrid partials
+    const unsigned grid = std::min(slice_grid(a.num_tiles, n_cus, 2), kProductMaxGrid);
+    hipError_t e = dispatch_k0_form(a.prog, [&](auto k, auto form) {
+        hipExtLaunchKernelGGL((eval_slice_sum_product<k.value, form.value>), dim3(grid), dim3(512), 0, stream, ev0, ev1, 0,
+                              a, g);
+    });
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(slice_product_finish_kernel, dim3(1), dim3(64), 0, stream, g.workspace, (int)grid, base_outer,
+                       base_inner, out, out_slots, count_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_aggregate_arrays(const int64_t* x, const uint64_t* valid, const uint64_t* d_count, uint64_t max_n,
                                    uint32_t ops, int type, int64_t* workspace, int64_t* out, hipStream_t stream) {
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((max_n + 2047) / 2048, kAggMaxGrid));
@@ -4993,6 +5421,43 @@ hipError_t launch_aggregate_arrays_grouped(const int64_t* x, const uint64_t* val
     GroupAggArgs none{};
     hipLaunchKernelGGL(aggregate_grouped_finish_kernel, dim3(n_groups), dim3(64), 0, stream, partials, (int)grid, none, 1,
                        ops, type, (int64_t)0, 0, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_eval_slice_sum_product_grouped(const EvalArgs& a, const SliceProductArgs& g, const GroupAggArgs& q,
+                                                 int64_t base_outer, int64_t base_inner, int n_cus, int64_t* out,
+                                                 hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+    constexpr uint32_t limit = kProductGroupBatch;
+    if (g.n_outer > kMaxSlices || g.n_inner > g.n_outer || a.num_tiles == 0 || !q.partials || q.n2 > 2 || q.n1 == 0 ||
+        q.n1 > (q.n2 ? limit / 2 : limit))
+        return hipErrorInvalidValue;
+    const unsigned grid = slice_grid(a.num_tiles, n_cus, 1);  // one workgroup per CU at the kernel's register count
+    const bool two = q.n2 != 0;
+    hipError_t e = dispatch_k0_form(a.prog, [&](auto k, auto form) {
+        if (two)
+            hipExtLaunchKernelGGL((eval_slice_sum_product_grouped<k.value, form.value, true>), dim3(grid), dim3(512), 0,
+                                  stream, ev0, ev1, 0, a, g, q);
+        else
+            hipExtLaunchKernelGGL((eval_slice_sum_product_grouped<k.value, form.value, false>), dim3(grid), dim3(512), 0,
+                                  stream, ev0, ev1, 0, a, g, q);
+    });
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sum_product_grouped_finish_kernel, dim3(limit), dim3(64), 0, stream, q.partials, (int)grid, q, 0,
+                       base_outer, base_inner, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_sum_product_arrays_grouped(const int64_t* xa, const uint64_t* va, const int64_t* xb, const uint64_t* vb,
+                                             const GroupColArgs& gc, uint32_t n_groups, const uint64_t* d_count,
+                                             uint64_t max_n, int64_t* partials, int64_t* out, hipStream_t stream) {
+    if (n_groups == 0 || n_groups > CUBIT_AGG_MAX_GROUPS || !partials) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((max_n + 16383) / 16384, kProductColGrid));
+    hipLaunchKernelGGL(sum_product_arrays_grouped_kernel, dim3(grid), dim3(256), 0, stream, xa, va, xb, vb, gc, n_groups,
+                       d_count, max_n, partials);
+    GroupAggArgs none{};
+    hipLaunchKernelGGL(sum_product_grouped_finish_kernel, dim3(n_groups), dim3(64), 0, stream, partials, (int)grid, none, 1,
+                       (int64_t)0, (int64_t)0, out);
     return hipGetLastError();
 }
 

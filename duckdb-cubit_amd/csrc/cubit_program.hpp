@@ -334,6 +334,87 @@ inline bool grouped_from_slices(bool force_slices, bool force_column, bool usabl
                             n_probed, 0.0);
 }
 
+// ---- sum(a · b) from the bit slices of two columns (cubit_table_sum_product's slice path,
+// cubit_bitslice_sum_product; Rinfret et al. 2001)
+//
+// With ua = a - base_a and ub = b - base_b the offsets the slices hold, A_i / B_j their slices,
+// V = F ∧ valid_a ∧ valid_b and n = |V|:
+//   Σ a·b  = n·base_a·base_b + base_a·Σub + base_b·Σua + Σ ua·ub
+//   Σua    = Σ_i 2^i·popc(V ∧ A_i)   (Σub likewise)
+//   Σua·ub = Σ_i Σ_j 2^(i+j)·popc(V ∧ A_i ∧ B_j)
+// all modulo 2^128 with the bases sign-extended: the exact two's-complement 128-bit sum for any slice
+// counts 0 … 64, INT64_MIN … INT64_MAX included. The kernel keeps a group of up to kProductInner
+// slices of the operand with fewer slices (the inner one) masked in registers and streams the other's
+// (the outer one's) past them; a wider inner operand takes further groups, each streaming the outer
+// slices again.
+constexpr uint32_t kProductInner = 8;  // inner slices held in registers per pass over the outer slices
+
+// x·2^s mod 2^128, s < 128
+CUBIT_HD inline U128 u128_shl_wide(uint64_t x, uint32_t s) { return s < 64 ? u128_shl(x, s) : U128{0, x << (s - 64)}; }
+// x·m mod 2^128, m sign-extended: the unsigned product less x·2^64 when m is negative
+CUBIT_HD inline U128 u128_mul_s64(U128 x, int64_t m) {
+    U128 p = u128_mul(x.lo, (uint64_t)m);
+    p.hi += x.hi * (uint64_t)m;
+    if (m < 0) p.hi -= x.lo;
+    return p;
+}
+// {sum_lo, sum_hi} of Σ a·b from cross = Σ ua·ub, sum_ua, sum_ub (each mod 2^128) and n
+CUBIT_HD inline void slice_product_combine(int64_t base_a, int64_t base_b, uint64_t n, U128 cross, U128 sum_ua,
+                                           U128 sum_ub, int64_t out[2]) {
+    U128 s = u128_mul_s64(u128_mul_s64(U128{n, 0}, base_a), base_b);
+    s = u128_add(s, u128_mul_s64(sum_ub, base_a));
+    s = u128_add(s, u128_mul_s64(sum_ua, base_b));
+    s = u128_add(s, cross);
+    out[0] = (int64_t)s.lo;
+    out[1] = (int64_t)s.hi;
+}
+
+// passes over the outer slices: one per group of kProductInner inner slices (one with no inner slice)
+inline uint32_t product_passes(uint32_t n_in) { return std::max(1u, (n_in + kProductInner - 1) / kProductInner); }
+// the bits of a live row the slice path reads: the K leaves, the validities, each inner slice once and
+// the outer slices once per pass
+inline uint32_t product_slice_bits(uint32_t n_a, uint32_t n_b, uint32_t k_leaves, bool nullable_a, bool nullable_b) {
+    const uint32_t n_in = std::min(n_a, n_b), n_out = std::max(n_a, n_b);
+    return k_leaves + (nullable_a ? 1u : 0u) + (nullable_b ? 1u : 0u) + n_in + n_out * product_passes(n_in);
+}
+// Which path cubit_table_sum_product takes, by bytes alone:
+//   slices: product_slice_bits/8 bytes per live row, whatever the filter keeps;
+//   column: the fused kernel (eval_sum_product) reads K/8 bytes per live row and per operand one
+//           128-byte line per estimated qualifying row, never more than the 8·rows bytes the column
+//           has; b decoded from b_decode index leaves costs b_decode/8 bytes per live row instead, and
+//           nothing when the filter pins it to one value (b_decode = 0; -1: b is gathered).
+// Without a force flag the slices are taken only when usable, in one streaming pass
+// (n_in ≤ kProductInner) and their bytes are not more; a wider inner operand runs from slices only
+// when forced. Every term is a whole number of eighths of a byte, as path_from_slices'. The constants
+// are derived from bytes alone: at 612 M rows, 24 × 4 slices and K = 1 the rule's crossover is 1.37 % of
+// the rows, and scripts/slice_product_timing.py measured the column faster at 1 % and the slices
+// faster from 10 % up.
+inline bool sum_product_from_slices(bool force_slices, bool force_column, bool usable, uint32_t n_a, uint32_t n_b,
+                                    uint32_t k_leaves, bool nullable_a, bool nullable_b, uint64_t live_rows, uint64_t rows,
+                                    uint64_t est_rows, int b_decode) {
+    if (force_column || !usable) return false;
+    if (force_slices) return true;
+    if (std::min(n_a, n_b) > kProductInner) return false;
+    const double slices = (double)product_slice_bits(n_a, n_b, k_leaves, nullable_a, nullable_b) / 8.0 * (double)live_rows;
+    const double gather = std::min(128.0 * (double)est_rows, 8.0 * (double)rows);
+    double column = (double)k_leaves / 8.0 * (double)live_rows + gather;
+    column += b_decode < 0 ? gather : (double)b_decode / 8.0 * (double)live_rows;
+    return slices <= column;
+}
+// Which path cubit_table_sum_product_grouped takes (path_from_slices; both operands and each group
+// column are probed: elem_bytes holds a's size, b's, then each group column's):
+//   slices: each launch of eval_slice_sum_product_grouped reads product_slice_bits and its own group
+//           leaves per live row: slice_bits = that sum over the launches (group_batches_bits).
+// The structural condition is the ungrouped rule's: without a force flag, one streaming pass.
+constexpr uint32_t kProductGroupBatch = 4;  // groups per launch of the grouped kernel
+inline bool sum_product_grouped_from_slices(bool force_slices, bool force_column, bool usable, uint32_t n_a, uint32_t n_b,
+                                            uint64_t slice_bits, uint32_t k_leaves, uint64_t live_rows, uint64_t rows,
+                                            uint64_t est_rows, const uint64_t* elem_bytes, uint32_t n_probed) {
+    if (!force_slices && std::min(n_a, n_b) > kProductInner) return false;
+    return path_from_slices(force_slices, force_column, usable, slice_bits, k_leaves, live_rows, rows, est_rows, elem_bytes,
+                            n_probed, 0.0);
+}
+
 // ---- selection by rank from a bit-sliced index (cubit_table_select; O'Neil & Quass 1997 §3)
 //
 // A radix select over the offsets u = key - base, most significant slices first. A step histograms

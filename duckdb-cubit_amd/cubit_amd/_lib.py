@@ -55,6 +55,7 @@ SUM_GATHER_B = 1
 SUM_NO_ZONEMAP = 2
 SUM_PACKED_A = 4
 SUM_PLAIN_A = 8
+SUM_FROM_SLICES, SUM_FROM_COLUMN = 16, 32
 AGG_SUM, AGG_MIN, AGG_MAX = 1, 2, 4
 AGG_ALL = AGG_SUM | AGG_MIN | AGG_MAX
 AGG_FROM_SLICES, AGG_FROM_COLUMN, AGG_NO_ZONEMAP = 16, 32, 64
@@ -204,6 +205,9 @@ GPU_SIGNATURES = {
     "cubit_table_column_statistics": (C.c_int, [_P, C.c_int, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(C.c_int),
                                                 C.POINTER(C.c_int)]),
     "cubit_table_sum_product": (C.c_int, [_P, _P, _U32, _P, C.c_int, C.c_int, _P, _P, _U32]),
+    "cubit_table_last_sum_product": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(_U32)]),
+    "cubit_table_sum_product_grouped": (C.c_int, [_P, _P, _U32, _P, C.c_int, C.c_int, _P, _U32, _U32, _P, _U32]),
+    "cubit_bitslice_sum_product": (C.c_int, [_P, _P, _U32, _P, _I64, _P, _U32, _P, _I64, _P, _U64, _P]),
     "cubit_table_last_sum_decode": (C.c_int, [_P, C.POINTER(_U32)]),
     "cubit_table_last_sum_packed": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "cubit_table_aggregate": (C.c_int, [_P, _P, _U32, _P, C.c_int, _U32, _P]),

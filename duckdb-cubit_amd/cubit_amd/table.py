@@ -615,9 +615,14 @@ class CubitTable:
 
     def sum_product(self, col_a: int, col_b: int, filter_set: Optional[TableFilterSet] = None,
                     residual: Optional[Residual] = None, txn: Optional[L.Txn] = None,
-                    gather_b: bool = False, zonemap: bool = True, packed_a: bool = True) -> Tuple[int, int]:
+                    gather_b: bool = False, zonemap: bool = True, packed_a: bool = True,
+                    path: Optional[str] = None) -> Tuple[int, int]:
         """SELECT sum(a*b), count(*) WHERE <filter> in one fused pass → (sum as a Python int
-        of the 128-bit DECIMAL storage, qualifying rows)."""
+        of the 128-bit DECIMAL storage, qualifying rows). path: None lets the library choose,
+        "slices" forces both columns' bit-sliced indexes, "column" the fused gather."""
+        if path not in (None, "slices", "column"):
+            raise ValueError(f"path {path!r}")
+        force = {None: 0, "slices": L.SUM_FROM_SLICES, "column": L.SUM_FROM_COLUMN}[path]
         plan = serialize(filter_set, residual)
         arr = to_ctypes(plan.nodes)
         out = self.ctx.alloc(16)
@@ -627,13 +632,52 @@ class CubitTable:
                                                  C.c_void_p(out.addr), C.c_void_p(cnt.addr),
                                                  (L.SUM_GATHER_B if gather_b else 0)
                                                  | (0 if zonemap else L.SUM_NO_ZONEMAP)
-                                                 | (0 if packed_a else L.SUM_PLAIN_A)))
+                                                 | (0 if packed_a else L.SUM_PLAIN_A) | force))
         self.ctx.check()
         lo, hi = (int(x) for x in out.download(np.int64, 2))
         n = int(cnt.download(np.uint64, 1)[0])
         out.free()
         cnt.free()
         return (hi << 64) + (lo & (2 ** 64 - 1)), n
+
+    def sum_product_by(self, col_a: int, col_b: int, by, filter_set: Optional[TableFilterSet] = None,
+                       residual: Optional[Residual] = None, txn: Optional[L.Txn] = None, path: Optional[str] = None,
+                       zonemap: bool = True) -> Dict[tuple, Tuple[int, int, int]]:
+        """SELECT by…, sum(a*b), count(*) WHERE <filter> GROUP BY by… → {key tuple: (sum, count_valid,
+        count_rows)}, the keys as aggregate_by gives them; count_valid counts the rows where neither
+        a nor b is NULL. Groups without a qualifying row are left out. path and zonemap as
+        sum_product()'s."""
+        if path not in (None, "slices", "column"):
+            raise ValueError(f"path {path!r}")
+        flags = {None: 0, "slices": L.SUM_FROM_SLICES, "column": L.SUM_FROM_COLUMN}[path]
+        flags |= 0 if zonemap else L.SUM_NO_ZONEMAP
+        groups = self.aggregate_groups(by)
+        cols, arr = self._group_cols(by)
+        plan = serialize(filter_set, residual)
+        nodes = to_ctypes(plan.nodes)
+        ng = len(groups)
+        out = self.ctx.alloc(max(ng, 1) * 32)
+        try:
+            L.check(self.lib.cubit_table_sum_product_grouped(self.handle, nodes, len(plan.nodes),
+                                                             C.byref(txn) if txn is not None else None, col_a, col_b,
+                                                             arr, len(cols), flags, C.c_void_p(out.addr), ng))
+            self.ctx.check()
+            res = out.download(np.int64, ng * 4).reshape(ng, 4) if ng else np.zeros((0, 4), dtype=np.int64)
+        finally:
+            out.free()
+        result = {}
+        for key, row in zip(groups, res):
+            lo, hi, cv, cr = (int(x) for x in row)
+            if cr:
+                result[key] = ((hi << 64) + (lo & (2 ** 64 - 1)), cv, cr)
+        return result
+
+    def last_sum_product(self):
+        """(whether the last sum_product() / sum_product_by() read the bit slices, the slice kernel's
+        launches — 0 from the column)."""
+        fs, nl = C.c_int(), C.c_uint32()
+        L.check(self.lib.cubit_table_last_sum_product(self.handle, C.byref(fs), C.byref(nl)))
+        return bool(fs.value), int(nl.value)
 
     def aggregate(self, col: int, filter_set: Optional[TableFilterSet] = None, residual: Optional[Residual] = None,
                   txn: Optional[L.Txn] = None, ops: Optional[int] = None, path: Optional[str] = None,

@@ -784,8 +784,53 @@ int cubit_table_last_zones(cubit_table *t, uint32_t *evaluated, uint32_t *zones)
  * CUBIT_SUM_PACKED_A names the default. */
 #define CUBIT_SUM_PACKED_A 4u
 #define CUBIT_SUM_PLAIN_A 8u
+/* A second path answers the same sum from the operands' bit slices without reading either column
+ * (Rinfret et al. 2001): with ua = a - base_a, ub = b - base_b the offsets the slices hold and
+ * V = F AND valid_a AND valid_b, sum(a * b) = |V| * base_a * base_b + base_a * sum(ub) + base_b * sum(ua)
+ * + sum over i, j of 2^(i+j) * popcount(V AND A_i AND B_j), carried modulo 2^128: the same exact
+ * two's-complement sum. It is usable when both columns carry a non-empty bit-sliced index
+ * (CUBIT_INDEX_SLICED), cubit_table_use_sliced is on and no update record of either is visible to txn;
+ * it reads (K + validities + n_in + n_out * passes) / 8 bytes per row of the evaluated zones whatever
+ * the filter keeps (n_in <= n_out the slice counts, passes = max(1, ceil(n_in / 8))). Without a force
+ * flag it runs when usable, n_in <= 8 (one pass over the outer slices) and its bytes are not more than
+ * the fused gather's estimate. CUBIT_SUM_FROM_SLICES forces it (CUBIT_ERR_INVALID when not usable),
+ * CUBIT_SUM_FROM_COLUMN forces the fused gather; both together are CUBIT_ERR_INVALID.
+ * cubit_table_last_sum_product tells which ran and the slice kernel's launches (0 from the column;
+ * either pointer may be NULL); cubit_table_last_sliced counts one more leaf per operand read from
+ * its slices. */
+#define CUBIT_SUM_FROM_SLICES 16u /* as CUBIT_AGG_FROM_SLICES */
+#define CUBIT_SUM_FROM_COLUMN 32u /* as CUBIT_AGG_FROM_COLUMN */
 int cubit_table_sum_product(cubit_table *t, const cubit_filter_node *nodes, uint32_t n_nodes, const cubit_txn *txn,
                             int col_a, int col_b, int64_t *d_out, uint64_t *d_count, uint32_t flags);
+int cubit_table_last_sum_product(cubit_table *t, int *from_slices, uint32_t *n_launches);
+/* SELECT g1 [, g2], sum(a * b), count(*) WHERE <filter> GROUP BY g1 [, g2] (the shape of TPC-H Q1's
+ * sum(l_extendedprice * l_discount) per l_returnflag, l_linestatus). Groups and their numbering are
+ * exactly cubit_table_aggregate_groups', with cubit_table_aggregate_grouped's refusals (an every-value
+ * EQUALITY index on each group column, CUBIT_AGG_MAX_GROUPS, cap_groups below the group count is
+ * CUBIT_ERR_CAPACITY). For group g, d_out + 4 * g (device, cap_groups * 4 int64) =
+ * {sum_lo, sum_hi, count_valid, count_rows}: count_rows = the group's qualifying rows, count_valid =
+ * those where neither a nor b is NULL (only they add to the sum). A group with no qualifying row has
+ * four zeros; so has every group of an empty partition or under a filter that folds to FALSE.
+ *   From the slices (both operands usable as above, and no update record of a, b or a group column
+ * visible to txn): the fused kernel takes 4 groups per launch (4 x 1 bitvectors of one group column,
+ * 2 x 2 of two), each launch reading the ungrouped bytes and its group bitvectors; more groups run as
+ * further launches. From the column: scan into scratch, probe a, b and each group column with
+ * validity (visible MVCC updates applied), reduce per group in 128 bits. flags: CUBIT_SUM_FROM_SLICES |
+ * _FROM_COLUMN | _NO_ZONEMAP (anything else is CUBIT_ERR_INVALID); without a force flag the slices run
+ * when usable, n_in <= 8 and estimated to move no more bytes. cubit_table_last_sum_product reports the
+ * path and the fused kernel's launches. */
+int cubit_table_sum_product_grouped(cubit_table *t, const cubit_filter_node *nodes, uint32_t n_nodes,
+                                    const cubit_txn *txn, int col_a, int col_b, const int *group_cols,
+                                    uint32_t n_group_cols, uint32_t flags, int64_t *d_out, uint32_t cap_groups);
+/* The slice path's kernel on a caller's slices, with the conventions of cubit_bitslice_aggregate: each
+ * operand's slices (0 ... 64 device pointers, each cubit_padded_words(n_rows) words, 16-byte aligned),
+ * its validity (NULL = every row valid) and the base key its offsets count from; d_filter as there.
+ * d_out (device, 4 int64) = {sum_lo, sum_hi, count_valid, count_rows}: count_valid = the qualifying
+ * rows where neither operand is NULL. */
+int cubit_bitslice_sum_product(cubit_ctx *ctx, const uint64_t *const *d_a_slices, uint32_t n_a,
+                               const uint64_t *d_a_validity, int64_t base_a, const uint64_t *const *d_b_slices,
+                               uint32_t n_b, const uint64_t *d_b_validity, int64_t base_b, const uint64_t *d_filter,
+                               uint64_t n_rows, int64_t *d_out);
 /* How the last sum_product read b: number of values decoded from the index (0 = gathered;
  * 1 = the filter pins b to one value, which is multiplied in as a constant: no leaf is read). */
 int cubit_table_last_sum_decode(cubit_table *t, uint32_t *n_values);
