@@ -92,6 +92,7 @@ struct cubit_ctx {
     hipEvent_t gkeys_ev = nullptr;
     bool gkeys_pending = false;
     int64_t* sel = nullptr;      // workspace of the select kernels (kSelectWorkspace int64; ensure_select)
+    int64_t* gsel = nullptr;     // … of the grouped select's (kSelectGroupWorkspace int64; ensure_select_grouped)
     uint64_t* ticket = nullptr;  // claim ticket of the evaluate kernels (EvalArgs::ticket)
     uint64_t* flags = nullptr;   // look-back flag words of eval_decode_lookback (EvalArgs::flags)
     uint64_t epoch = 0;          // the last look-back launch's epoch (EvalArgs::epoch)
@@ -162,6 +163,16 @@ int ensure_select(cubit_ctx* ctx) {
     if (hipMalloc(&ctx->sel, kSelectWorkspace * sizeof(int64_t)) != hipSuccess) {
         ctx->sel = nullptr;
         return fail(CUBIT_ERR_OOM, "select workspace allocation failed");
+    }
+    return CUBIT_OK;
+}
+
+// the grouped select's workspace, allocated on the context when the first grouped select needs it
+int ensure_select_grouped(cubit_ctx* ctx) {
+    if (ctx->gsel) return CUBIT_OK;
+    if (hipMalloc(&ctx->gsel, kSelectGroupWorkspace * sizeof(int64_t)) != hipSuccess) {
+        ctx->gsel = nullptr;
+        return fail(CUBIT_ERR_OOM, "grouped select workspace allocation failed");
     }
     return CUBIT_OK;
 }
@@ -459,6 +470,7 @@ int cubit_ctx_destroy(cubit_ctx* ctx) {
     if (ctx->gkeys_pending) (void)hipEventSynchronize(ctx->gkeys_ev);
     if (ctx->gagg) (void)hipFree(ctx->gagg);
     if (ctx->sel) (void)hipFree(ctx->sel);
+    if (ctx->gsel) (void)hipFree(ctx->gsel);
     if (ctx->gkeys_dev) (void)hipFree(ctx->gkeys_dev);
     if (ctx->gkeys_host) (void)hipHostFree(ctx->gkeys_host);
     if (ctx->gkeys_ev) (void)hipEventDestroy(ctx->gkeys_ev);
@@ -949,6 +961,61 @@ int cubit_bitslice_select(cubit_ctx* ctx, const uint64_t* const* d_slices, uint3
     return CUBIT_OK;
 }
 
+int cubit_bitslice_select_grouped(cubit_ctx* ctx, const uint64_t* const* d_slices, uint32_t n_slices,
+                                  const uint64_t* d_validity, const uint64_t* d_filter, const uint64_t* const* d_groups,
+                                  uint32_t n_groups, uint64_t n_rows, int type, int64_t base, int mode, uint64_t k, double q,
+                                  int64_t* d_out) {
+    if (!ctx || !d_out || !d_groups || (n_slices && !d_slices)) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(ctx);
+    if (n_slices > kMaxSlices) return fail(CUBIT_ERR_INVALID, "%u slices (0 … 64)", n_slices);
+    if (n_groups == 0 || n_groups > CUBIT_AGG_MAX_GROUPS)
+        return fail(CUBIT_ERR_INVALID, "%u groups (1 … %d)", n_groups, CUBIT_AGG_MAX_GROUPS);
+    if (mode != CUBIT_SELECT_RANK && mode != CUBIT_SELECT_RANK_DESC && mode != CUBIT_SELECT_QUANTILE)
+        return fail(CUBIT_ERR_INVALID, "mode %d", mode);
+    if (mode == CUBIT_SELECT_QUANTILE && !(q >= 0.0 && q <= 1.0)) return fail(CUBIT_ERR_INVALID, "quantile %g outside [0, 1]", q);
+    if (type != CUBIT_TYPE_INT32 && type != CUBIT_TYPE_INT64 && type != CUBIT_TYPE_VARCHAR && !type_is_keyed(type))
+        return fail(CUBIT_ERR_UNSUPPORTED, "type %d", type);
+    if (n_rows >= (1ull << 47)) return fail(CUBIT_ERR_INVALID, "%llu rows exceed 2^47", (unsigned long long)n_rows);
+    auto aligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    if (!aligned(d_filter) || !aligned(d_validity)) return fail(CUBIT_ERR_INVALID, "bitvectors must be 16-byte aligned");
+    SliceSelectArgs g{};
+    for (uint32_t s = 0; s < n_slices; ++s) {
+        if (!d_slices[s] || !aligned(d_slices[s])) return fail(CUBIT_ERR_INVALID, "slice %u is null or unaligned", s);
+        g.slices.s[s] = const_cast<uint64_t*>(d_slices[s]);
+    }
+    for (uint32_t i = 0; i < n_groups; ++i)
+        if (!d_groups[i] || !aligned(d_groups[i])) return fail(CUBIT_ERR_INVALID, "group %u is null or unaligned", i);
+    if (int rc = set_device(ctx)) return rc;
+    HIP_CHECK(hipMemsetAsync(d_out, 0, (size_t)n_groups * 6 * sizeof(int64_t), ctx->stream));
+    if (n_rows == 0) return CUBIT_OK;  // no rows: zero counts, nothing to launch
+    if (int rc = ensure_select_grouped(ctx)) return rc;
+    if (int rc = ensure_tmp(ctx, padded_words(n_rows))) return rc;  // the candidate bitvector
+    g.n_slices = n_slices;
+    g.validity = d_validity;
+    g.cand = reinterpret_cast<uint64_t*>(ctx->tmp_ids);
+    g.workspace = ctx->gsel;
+    EvalProgram prog{};
+    if (d_filter) {  // a one-leaf program; NULL: the zero-leaf form, every row below n_rows
+        prog.leaf[0] = d_filter;
+        prog.n_leaves = 1;
+    }
+    EvalArgs a;
+    if (int rc = tile_eval_args(ctx, prog, n_rows, 0, kAggTileWords, {}, a)) return rc;
+    for (uint32_t g0 = 0; g0 < n_groups; g0 += kGroupBatchSelect) {  // a batch through all its passes, then the next
+        GroupAggArgs qa{};
+        qa.n1 = std::min(kGroupBatchSelect, n_groups - g0);
+        for (uint32_t j = 0; j < kGroupBatchSum; ++j) qa.group[j] = kNoGroup;
+        for (uint32_t x = 0; x < qa.n1; ++x) {
+            qa.e1[x] = d_groups[g0 + x];
+            qa.group[x] = g0 + x;
+        }
+        hipEvent_t e0, e1;
+        if (int rc = timing_events(ctx, e0, e1)) return rc;
+        HIP_CHECK(launch_slice_select_grouped(a, g, qa, mode, k, q, type, base, ctx->n_cus, d_out, ctx->stream, nullptr, e0, e1));
+    }
+    return CUBIT_OK;
+}
+
 }  // extern "C"
 
 extern "C" int cubit_bitvector_eval(cubit_ctx* ctx, const uint64_t* const* d_leaves, uint32_t n_leaves,
@@ -1279,6 +1346,9 @@ struct cubit_table {
     // the last cubit_table_aggregate_grouped: its path, group count and fused-kernel launches
     bool last_grouped_slices = false;
     uint32_t last_grouped_groups = 0, last_grouped_launches = 0;
+    // the last cubit_table_select_grouped: its path, group count, batches and passes per batch
+    bool last_gsel_slices = false;
+    uint32_t last_gsel_groups = 0, last_gsel_launches = 0, last_gsel_passes = 0;
     // Derived leaves: combinations of one column's table-owned bitvectors that scans keep asking
     // for (a RANGE interval's L(hi) AND NOT L(lo), a union of EQUALITY / BINS leaves), each kept
     // as one bitvector once it has been planned often enough (derive_leaves). Dropped with the
@@ -5998,6 +6068,108 @@ extern "C" int cubit_table_last_grouped(cubit_table* t, int* from_slices, uint32
     if (from_slices) *from_slices = t->last_grouped_slices ? 1 : 0;
     if (n_groups) *n_groups = t->last_grouped_groups;
     if (n_launches) *n_launches = t->last_grouped_launches;
+    return CUBIT_OK;
+}
+
+// cubit_table_select per group: cubit_table_aggregate_grouped's structure with a radix select in the
+// reduction's place. From the slices a batch of groups runs through all its passes over the one
+// scratch candidate bitvector before the next batch starts; from the column every group's select
+// runs at once over the probed values. select_grouped_from_slices (cubit_program.hpp) chooses.
+extern "C" int cubit_table_select_grouped(cubit_table* t, const cubit_filter_node* nodes, uint32_t n_nodes,
+                                          const cubit_txn* txn, int col, const int* group_cols, uint32_t n_group_cols,
+                                          int mode, uint64_t k, double q, uint32_t flags, int64_t* d_out,
+                                          uint32_t cap_groups) {
+    if (!t || !d_out || !group_cols) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    if (n_nodes && !nodes) return fail(CUBIT_ERR_INVALID, "nodes is null");
+    if (mode != CUBIT_SELECT_RANK && mode != CUBIT_SELECT_RANK_DESC && mode != CUBIT_SELECT_QUANTILE)
+        return fail(CUBIT_ERR_INVALID, "mode %d", mode);
+    if (mode == CUBIT_SELECT_QUANTILE && !(q >= 0.0 && q <= 1.0)) return fail(CUBIT_ERR_INVALID, "quantile %g outside [0, 1]", q);
+    if (flags & ~(CUBIT_SELECT_FROM_SLICES | CUBIT_SELECT_FROM_COLUMN | CUBIT_SELECT_NO_ZONEMAP))
+        return fail(CUBIT_ERR_INVALID, "flags %u", flags);
+    SlicePlan p;
+    if (int rc = forced_path(flags & CUBIT_SELECT_FROM_SLICES, flags & CUBIT_SELECT_FROM_COLUMN, p)) return rc;
+    auto cit = t->cols.find(col);
+    if (cit == t->cols.end()) return fail(CUBIT_ERR_INVALID, "column %d not registered", col);
+    const Column& c = cit->second;
+    GroupCol gc[CUBIT_AGG_MAX_GROUP_COLS];
+    uint32_t n1 = 0, n2 = 1;
+    if (int rc = group_columns(t, group_cols, n_group_cols, gc, &n1, &n2)) return rc;
+    const uint32_t n_groups = n1 * n2;
+    if (cap_groups < n_groups) return fail(CUBIT_ERR_CAPACITY, "%u groups, room for %u", n_groups, cap_groups);
+    // an update record of the value column or of a group column rules the slices out
+    int ruling[1 + CUBIT_AGG_MAX_GROUP_COLS] = {col};
+    for (uint32_t i = 0; i < n_group_cols; ++i) ruling[1 + i] = gc[i].col;
+    if (int rc = bind_slices(t, txn, col, c, ruling, 1 + n_group_cols, p)) return rc;
+    cubit_ctx* ctx = t->ctx;
+    t->last_gsel_slices = false;
+    t->last_gsel_groups = n_groups;
+    t->last_gsel_launches = t->last_gsel_passes = 0;
+    if (n_groups == 0) return CUBIT_OK;
+    // every group starts as six zeros: the kernels write the groups that reach them
+    HIP_CHECK(hipMemsetAsync(d_out, 0, (size_t)n_groups * 6 * sizeof(int64_t), ctx->stream));
+    if (int rc = plan_slice_query(t, nodes, n_nodes, txn, !(flags & CUBIT_SELECT_NO_ZONEMAP), p)) return rc;
+    if (p.no_rows) return CUBIT_OK;
+    if (int rc = ensure_select_grouped(ctx)) return rc;
+
+    std::vector<GroupLeaf> leaves[CUBIT_AGG_MAX_GROUP_COLS];
+    group_leaves(gc, n_group_cols, leaves);
+    const bool two = n_group_cols > 1;
+    bool swapped = false;
+    // (row_bits decides only which column takes the side of 2: a launch's passes all read its leaves)
+    const std::vector<GroupBatch> batches =
+        split_group_batches((uint32_t)leaves[0].size(), two ? (uint32_t)leaves[1].size() : 0u, two, kGroupBatchSelect,
+                            p.bits() + p.em.prog.n_leaves + (c.validity ? 1u : 0u), &swapped);
+    uint64_t elem_bytes[1 + CUBIT_AGG_MAX_GROUP_COLS] = {p.elem_bytes(), 0, 0};
+    for (uint32_t i = 0; i < n_group_cols; ++i) elem_bytes[1 + i] = type_is32(gc[i].c->type) ? 4 : 8;
+    if (select_grouped_from_slices(p.force_slices, p.force_column, p.sx != nullptr,
+                                   select_grouped_slice_bits(batches, p.bits(), p.em.prog.n_leaves, c.validity != nullptr),
+                                   p.em.prog.n_leaves, p.live_rows, t->n_rows, p.est_rows, elem_bytes, 1 + n_group_cols)) {
+        if (int rc = ensure_tmp(ctx, padded_words(t->n_rows))) return rc;  // the candidate bitvector
+        SliceSelectArgs g{};
+        g.slices = slice_set(*p.sx);
+        g.n_slices = p.bits();
+        g.validity = c.validity;
+        g.cand = reinterpret_cast<uint64_t*>(ctx->tmp_ids);
+        g.workspace = ctx->gsel;
+        EvalArgs a;  // (the kernels count each group's rows in their partials and take no ticket)
+        if (int rc = tile_eval_args(ctx, p.em.prog, t->n_rows, t->row_base, kAggTileWords, p.live, a)) return rc;
+        const std::vector<GroupLeaf>& la = leaves[swapped ? 1 : 0];
+        const std::vector<GroupLeaf>& lb = leaves[swapped ? 0 : 1];
+        for (const GroupBatch& b : batches) {  // a batch through all its passes, then the next
+            GroupAggArgs qa{};
+            fill_group_batch(b, la, lb, two, swapped, n2, qa);
+            hipEvent_t e0, e1;
+            if (int rc = timing_events(ctx, e0, e1)) return rc;
+            HIP_CHECK(launch_slice_select_grouped(a, g, qa, mode, k, q, c.type, p.sx->vmin, ctx->n_cus, d_out, ctx->stream,
+                                                  &t->last_gsel_passes, e0, e1));
+            t->last_gsel_launches++;
+        }
+        if (batches.empty()) t->last_gsel_passes = select_passes(p.bits(), kSelectChunk);
+        t->last_gsel_slices = true;
+        t->last_sliced++;
+        return CUBIT_OK;
+    }
+    // the column path: the value column and the group columns are probed
+    if (int rc = ensure_grouped(ctx)) return rc;  // (the slot keys' staging)
+    ColumnScratch cs;
+    if (int rc = decode_to_scratch(t, p, 1 + n_group_cols, cs)) return rc;
+    if (int rc = probe_impl(t, col, txn, cs.ids, cs.count, cs.cap, cs.values_of(0), cs.valid_of(0))) return rc;
+    GroupColArgs ga{};
+    if (int rc = probe_group_columns(t, txn, gc, n_group_cols, n2, cs, 1, ga)) return rc;
+    HIP_CHECK(launch_select_arrays_grouped(cs.values_of(0), cs.valid_of(0), ga, n_groups, cs.count, cs.cap, mode, k, q, c.type,
+                                           ctx->gsel, d_out, ctx->stream, &t->last_gsel_passes));
+    return CUBIT_OK;
+}
+
+extern "C" int cubit_table_last_select_grouped(cubit_table* t, int* from_slices, uint32_t* n_groups, uint32_t* n_launches,
+                                               uint32_t* n_passes) {
+    if (!t) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(t->ctx);
+    if (from_slices) *from_slices = t->last_gsel_slices ? 1 : 0;
+    if (n_groups) *n_groups = t->last_gsel_groups;
+    if (n_launches) *n_launches = t->last_gsel_launches;
+    if (n_passes) *n_passes = t->last_gsel_passes;
     return CUBIT_OK;
 }
 

@@ -369,6 +369,51 @@ hipError_t launch_eval_slice_sum_product_grouped(const EvalArgs& a, const SliceP
 hipError_t launch_sum_product_arrays_grouped(const int64_t* xa, const uint64_t* va, const int64_t* xb, const uint64_t* vb,
                                              const GroupColArgs& gc, uint32_t n_groups, const uint64_t* d_count,
                                              uint64_t max_n, int64_t* partials, int64_t* out, hipStream_t stream);
+// Selection by rank per group (cubit_table_select_grouped). The slice path runs a batch of up to
+// kGroupBatchSelect groups through all its passes over one candidate bitvector
+// (eval_slice_select_grouped, then slice_select_narrow_grouped per later chunk); the column path runs
+// every group at once over the probed values (select_arrays_grouped_kernel, kSelectGroupArrayBits bits
+// per pass). Either leaves, per workgroup and slot, kSelectSlotCols counters — the chunk's 2^4 buckets,
+// then the slot's rows (pass 0 only) — workgroup-major with a stride of n_slots · kSelectSlotCols, and
+// one workgroup after each pass (select_step_grouped_kernel) sums them and applies select_step to each
+// slot's SelectState. The workspace (kSelectGroupWorkspace int64, allocated on the context when the
+// first grouped select needs it): the partials, then CUBIT_AGG_MAX_GROUPS states, then as many
+// count_rows slots. out + 6·group = the six slots of launch_slice_select.
+static_assert(kSelectGroupArrayBits == kSelectChunk, "both paths' passes have the same buckets per slot");
+constexpr uint32_t kSelectSlotCols = (1u << kSelectChunk) + 1;
+constexpr uint64_t kSelectGroupSlotBlocks = (uint64_t)kAggMaxGrid * kGroupBatchSelect;  // slots × workgroups
+constexpr uint64_t kSelectGroupPartials = kSelectGroupSlotBlocks * kSelectSlotCols;
+constexpr unsigned kSelectGroupColGrid = 256;  // the column path's grid at most, and no more than fits:
+__host__ __device__ inline unsigned select_group_col_grid(uint32_t n_groups) {
+    const unsigned fit = (unsigned)(kSelectGroupSlotBlocks / (n_groups ? n_groups : 1));
+    return fit < kSelectGroupColGrid ? fit : kSelectGroupColGrid;
+}
+static_assert((uint64_t)kAggMaxGrid * kGroupBatchSelect * kSelectSlotCols <= kSelectGroupPartials, "the slice path's partials fit");
+static_assert(kSelectGroupSlotBlocks / CUBIT_AGG_MAX_GROUPS >= 1, "the column path's partials fit at any group count");
+constexpr uint64_t kSelectStateWords = sizeof(SelectState) / sizeof(int64_t);
+static_assert(sizeof(SelectState) % sizeof(int64_t) == 0, "a state is whole words");
+constexpr uint64_t kSelectGroupWorkspace =
+    kSelectGroupPartials + (uint64_t)CUBIT_AGG_MAX_GROUPS * kSelectStateWords + CUBIT_AGG_MAX_GROUPS;
+static_assert(kGroupBatchSelect <= CUBIT_AGG_MAX_GROUPS, "a batch's states and count_rows slots fit");
+__host__ __device__ inline SelectState* select_group_state(int64_t* workspace, uint32_t slot) {
+    return reinterpret_cast<SelectState*>(workspace + kSelectGroupPartials) + slot;
+}
+__host__ __device__ inline uint64_t* select_group_rows(int64_t* workspace, uint32_t slot) {
+    return reinterpret_cast<uint64_t*>(workspace + kSelectGroupPartials + (uint64_t)CUBIT_AGG_MAX_GROUPS * kSelectStateWords) +
+           slot;
+}
+// a / g as launch_slice_select's (no ticket: each group's rows are counted in its partials); q as
+// launch_eval_slice_aggregate_grouped's with q.n1 ≤ kGroupBatchSelect (half that with two group
+// columns; q.partials is not used). The same k / q for every group.
+hipError_t launch_slice_select_grouped(const EvalArgs& a, const SliceSelectArgs& g, const GroupAggArgs& q, int mode,
+                                       uint64_t k, double quantile, int type, int64_t base, int n_cus, int64_t* out,
+                                       hipStream_t stream, uint32_t* n_passes = nullptr, hipEvent_t ev0 = nullptr,
+                                       hipEvent_t ev1 = nullptr);
+// the same result for every group from x / valid and gc as launch_aggregate_arrays_grouped takes them
+hipError_t launch_select_arrays_grouped(const int64_t* x, const uint64_t* valid, const GroupColArgs& gc, uint32_t n_groups,
+                                        const uint64_t* d_count, uint64_t max_n, int mode, uint64_t k, double quantile,
+                                        int type, int64_t* workspace, int64_t* out, hipStream_t stream,
+                                        uint32_t* n_passes = nullptr);
 // after a merge: every 64-row word holding one of the m merged rows (ascending) sliced again from
 // the column as it stands
 hipError_t launch_bitslice_reslice(const int64_t* rows, uint64_t m, const void* col, int type, const uint64_t* validity,

@@ -2717,11 +2717,27 @@ __global__ __launch_bounds__(64) void slice_product_finish_kernel(const int64_t*
 // row, no workgroup waits on another, the stream orders the passes. A pair whose C is zero across
 // the wave skips its slice loads. Traffic: (K [+ 1] + 1 + 2b - d_last + 2·(passes - 1))·n/8 bytes
 // over the live zones.
-template <int CNT, int J, int IDX>
-__device__ __forceinline__ void select_hist_rec(const u64x2 (&w)[CNT > 0 ? CNT : 1], const u64x2& x, uint32_t px,
-                                                uint64_t (&h)[1 << kSelectChunk]) {
+// The counters of a histogram: 64 bits per bucket, or — the grouped kernels, which keep a histogram per
+// group — 16-bit fields, two per register. A thread adds at most the 64·NW = 256 rows it holds of a
+// tile to one field, so the grouped kernels fold the fields into 64-bit counters every
+// kSelectFoldTiles tiles (and at the end), before a field can wrap.
+template <int IDX>
+__device__ __forceinline__ void select_hist_add(uint64_t (&h)[1 << kSelectChunk], uint32_t px) {
+    h[IDX] += px;
+}
+constexpr uint32_t kSelectFoldTiles = 128;
+static_assert((uint64_t)kSelectFoldTiles * 4 * 64 <= 0xffffu, "a 16-bit field holds a thread's rows between two folds");
+struct PackedHist {
+    uint32_t v[(1 << kSelectChunk) / 2];
+};
+template <int IDX>
+__device__ __forceinline__ void select_hist_add(PackedHist& h, uint32_t px) {
+    h.v[IDX >> 1] += px << (16 * (IDX & 1));
+}
+template <int CNT, int J, int IDX, typename H>
+__device__ __forceinline__ void select_hist_rec(const u64x2 (&w)[CNT > 0 ? CNT : 1], const u64x2& x, uint32_t px, H& h) {
     if constexpr (J == CNT) {
-        h[IDX] += px;
+        select_hist_add<IDX>(h, px);
     } else {
         const u64x2 one = x & w[J];
         const uint32_t p1 = (uint32_t)(__popcll(one.x) + __popcll(one.y));
@@ -3269,6 +3285,351 @@ __global__ __launch_bounds__(64) void aggregate_grouped_finish_kernel(const int6
         o[3] = r[3];
         o[4] = (int64_t)part.valid;
         o[5] = (int64_t)part.rows;
+    }
+}
+
+// GROUP BY for the select: the radix select of eval_slice_select / slice_select_narrow for a batch of
+// NG = kGroupBatchSelect groups over ONE candidate bitvector. The groups of a call are pairwise
+// disjoint row sets (one equality leaf per group column, the NULL slot the complemented validity under
+// F), so C = ∪_g C_g keeps every group's candidates apart: group g's are C ∧ E_g.
+//   pass 0     eval_slice_select_grouped: F in registers, the batch's group leaves loaded once per pair
+//              of words (as eval_slice_aggregate_grouped), per group M_g = F ∧ E1 ∧ E2 counted into
+//              count_rows_g, C_g = M_g ∧ valid, C = ∪ C_g written to the candidate bitvector (every word
+//              of every evaluated tile) and the first chunk histogrammed per group over C_g;
+//   pass p > 0 slice_select_narrow_grouped reads C, loads the group leaves, the previous chunk and
+//              the next (all loads before use), keeps C' = C ∧ ∪_g (E_g ∧ [previous chunk = group g's
+//              chosen bucket]) — the bucket read from the group's device state, uniform; a group whose
+//              found is 0 keeps nothing — writes C' back in place (one thread per word) and histograms
+//              the next chunk per group.
+// After each pass select_step_grouped_kernel sums the workgroups' partials per slot and applies
+// select_step to each slot's state; after the last it writes the six result slots of each group. A
+// batch runs through all its passes before the next starts, so each batch's pass 0 rewrites the
+// candidate bitvector whole. Counters: per thread and group the 2^4 buckets as 16-bit fields
+// (PackedHist) and a 32-bit row count, folded by wave_sum into the wave's 64-bit LDS counters every
+// kSelectFoldTiles tiles and at the end; then workgroup, then the workgroup's partials. Exact integers,
+// no atomics, no workgroup waits on another, the stream orders the passes. A pair whose F (or C) is
+// zero across the wave loads nothing more; a group whose rows are zero across the wave skips its
+// arithmetic. Traffic per launch: (K [+ 1] + 1 + 2b - d_last + 2·(passes - 1) + leaves·passes)·n/8
+// bytes over the live zones.
+template <int NG>
+__device__ __forceinline__ void select_group_zero(uint64_t (*s_hist)[NG][kSelectSlotCols], int nwaves, int t, int threads) {
+    uint64_t* flat = &s_hist[0][0][0];
+    for (int i = t; i < nwaves * NG * (int)kSelectSlotCols; i += threads) flat[i] = 0;
+    __syncthreads();
+}
+// the thread's packed counters into its wave's LDS counters (every lane active); the fields restart
+template <int NG>
+__device__ __forceinline__ void select_group_fold(PackedHist (&h)[NG], uint32_t (&c_rows)[NG / 2],
+                                                  uint64_t (&s_wave)[NG][kSelectSlotCols], int lane) {
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+#pragma unroll
+        for (int i = 0; i < (1 << kSelectChunk) / 2; ++i) {
+            const uint64_t lo = wave_sum((uint64_t)(h[j].v[i] & 0xffffu)), hi = wave_sum((uint64_t)(h[j].v[i] >> 16));
+            if (lane == 0) {
+                s_wave[j][2 * i] += lo;
+                s_wave[j][2 * i + 1] += hi;
+            }
+            h[j].v[i] = 0;
+        }
+    }
+    // the rows: two groups' 16-bit fields per register, as the buckets
+#pragma unroll
+    for (int j = 0; j < NG / 2; ++j) {
+        const uint64_t lo = wave_sum((uint64_t)(c_rows[j] & 0xffffu)), hi = wave_sum((uint64_t)(c_rows[j] >> 16));
+        if (lane == 0) {
+            s_wave[2 * j][1 << kSelectChunk] += lo;
+            s_wave[2 * j + 1][1 << kSelectChunk] += hi;
+        }
+        c_rows[j] = 0;
+    }
+}
+// the waves' counters into this workgroup's partials (NG·kSelectSlotCols words at its index)
+template <int NG>
+__device__ __forceinline__ void select_group_publish(uint64_t (*s_hist)[NG][kSelectSlotCols], int nwaves,
+                                                     int64_t* workspace, int t, int threads) {
+    __syncthreads();
+    constexpr int COLS = NG * (int)kSelectSlotCols;
+    const uint64_t* flat = &s_hist[0][0][0];
+    for (int i = t; i < COLS; i += threads) {
+        uint64_t s = 0;
+        for (int w = 0; w < nwaves; ++w) s += flat[w * COLS + i];
+        workspace[(uint64_t)COLS * blockIdx.x + i] = (int64_t)s;
+    }
+}
+// the batch's group leaves of pair p: ea[x] (zero past q.n1) and, TWO, eb[0 … 1] (zero past q.n2)
+template <int NA, bool TWO, int THREADS>
+__device__ __forceinline__ void load_group_leaves(const GroupAggArgs& q, bool whole, uint64_t tile_word0, int p, int t,
+                                                  uint64_t n_words, u64x2 (&ea)[NA], u64x2 (&eb)[2]) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        eb[b] = u64x2{~0ull, ~0ull};
+        if (TWO) {
+            eb[b] = u64x2{0ull, 0ull};
+            if ((uint32_t)b < q.n2) eb[b] = load_pair<THREADS>(q.e2[b], (q.neg2 >> b) & 1u, whole, tile_word0, p, t, n_words);
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < NA; ++x) {
+        ea[x] = u64x2{0ull, 0ull};
+        if ((uint32_t)x < q.n1) ea[x] = load_pair<THREADS>(q.e1[x], (q.neg1 >> x) & 1u, whole, tile_word0, p, t, n_words);
+    }
+}
+
+template <int K, int FORM, bool TWO>
+__global__ __launch_bounds__(512, 2) void eval_slice_select_grouped(EvalArgs a, SliceSelectArgs g, GroupAggArgs q) {
+    constexpr int THREADS = 512, PAIRS = 2, NW = 4;
+    constexpr uint64_t TILE_WORDS = (uint64_t)THREADS * NW;
+    static_assert(TILE_WORDS == kAggTileWords, "a tile is one zone");
+    static_assert(PAIRS == 2, "the pair loop selects between two pairs");
+    static_assert(NW * 64 == 256, "the rows of a tile a thread adds to one field (kSelectFoldTiles)");
+    constexpr int NWAVES = THREADS / 64;
+    constexpr int NG = (int)kGroupBatchSelect, NA = TWO ? NG / 2 : NG, NB = TWO ? 2 : 1;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    __shared__ uint64_t s_hist[NWAVES][NG][kSelectSlotCols];
+    select_group_zero<NG>(s_hist, NWAVES, t, THREADS);
+    static_assert(NG % 2 == 0, "two groups' row counts share a register");
+    PackedHist h[NG];
+    uint32_t c_rows[NG / 2];  // 16-bit fields, folded with the buckets
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        c_rows[j >> 1] = 0;
+#pragma unroll
+        for (int i = 0; i < (1 << kSelectChunk) / 2; ++i) h[j].v[i] = 0;
+    }
+    // The first chunk is taken as kSelectChunk slices from top0 down: it may reach above the index's
+    // slices (it holds n_slices mod 4 of them, or none), and a slice that does not exist reads as zero,
+    // so the bucket is the chunk's bits all the same.
+    const int top0 = (int)select_chunk_low(g.n_slices, kSelectChunk, 0) + (int)kSelectChunk - 1;
+    uint32_t since = 0;
+    const uint32_t n_idx = a.num_tiles;
+    for (uint32_t i = blockIdx.x; i < n_idx; i += gridDim.x) {
+        const uint64_t tile_word0 = (uint64_t)tile_at(a, i) * TILE_WORDS;
+        uint64_t r[NW];
+        eval_tile<K, FORM, NW, THREADS>(a, tile_word0, t, r);
+        const bool whole = tile_word0 + TILE_WORDS <= a.n_words;
+        // one pair at a time, as eval_slice_aggregate_grouped (p is uniform, so the selects are scalar)
+#pragma unroll 1
+        for (int p = 0; p < PAIRS; ++p) {
+            u64x2 f;
+            f.x = p ? r[2] : r[0];
+            f.y = p ? r[3] : r[1];
+            const uint64_t pi = (tile_word0 >> 1) + (uint64_t)(p * THREADS + t);
+            if (__ballot((f.x | f.y) != 0) == 0) {  // no qualifying row in the wave's 128 words: no candidate
+                reinterpret_cast<u64x2*>(g.cand)[pi] = u64x2{0ull, 0ull};
+                continue;
+            }
+            u64x2 ea[NA], eb[2];
+            load_group_leaves<NA, TWO, THREADS>(q, whole, tile_word0, p, t, a.n_words, ea, eb);
+            u64x2 vv = {~0ull, ~0ull};
+            if (g.validity) vv = load_pair<THREADS>(g.validity, false, whole, tile_word0, p, t, a.n_words);
+            // C = ∪_g F ∧ E1_a ∧ E2_b ∧ valid = F ∧ valid ∧ (∪ E1) ∧ (∪ E2)
+            u64x2 ua = ea[0];
+#pragma unroll
+            for (int x = 1; x < NA; ++x) ua |= ea[x];
+            if (TWO) ua &= eb[0] | eb[1];
+            const u64x2 c = f & vv & ua;
+            reinterpret_cast<u64x2*>(g.cand)[pi] = c;  // the tile lies inside the padded candidate words
+            const bool none = __ballot((c.x | c.y) != 0) == 0;  // no candidate in the wave's 128 words: no slice is read
+            u64x2 w[kSelectChunk];
+#pragma unroll
+            for (int s = 0; s < (int)kSelectChunk; ++s) {
+                w[s] = u64x2{0ull, 0ull};
+                if (!none && top0 - s < (int)g.n_slices)
+                    w[s] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(g.slices.s[top0 - s]) + pi);
+            }
+#pragma unroll
+            for (int x = 0; x < NA; ++x) {
+#pragma unroll
+                for (int y = 0; y < NB; ++y) {
+                    const int j = NB * x + y;
+                    u64x2 m = f & ea[x] & eb[y];
+                    if (__ballot((m.x | m.y) != 0) == 0) continue;  // no row of this group in the wave's 128 words
+                    c_rows[j >> 1] += (uint32_t)(__popcll(m.x) + __popcll(m.y)) << (16 * (j & 1));
+                    m &= vv;
+                    if (__ballot((m.x | m.y) != 0) == 0) continue;
+                    select_hist_rec<(int)kSelectChunk, 0, 0>(w, m, (uint32_t)(__popcll(m.x) + __popcll(m.y)), h[j]);
+                }
+            }
+        }
+        if (++since == kSelectFoldTiles) {  // uniform: the tile loop is the workgroup's
+            select_group_fold<NG>(h, c_rows, s_hist[wave], lane);
+            since = 0;
+        }
+    }
+    select_group_fold<NG>(h, c_rows, s_hist[wave], lane);
+    select_group_publish<NG>(s_hist, NWAVES, g.workspace, t, THREADS);
+}
+
+// PC: the previous chunk's slices (its lowest at prev_low); the next chunk is whole, its lowest slice
+// at prev_low - kSelectChunk. a: the tile list of pass 0 (num_tiles, live); q: the batch of pass 0.
+template <int PC, bool TWO>
+__global__ __launch_bounds__(512, 2) void slice_select_narrow_grouped(EvalArgs a, SliceSelectArgs g, GroupAggArgs q,
+                                                                      uint32_t prev_low) {
+    constexpr int THREADS = 512, PAIRS = 2, NW = 4, NC = (int)kSelectChunk;
+    constexpr uint64_t TILE_WORDS = (uint64_t)THREADS * NW;
+    static_assert(NW * 64 == 256, "the rows of a tile a thread adds to one field (kSelectFoldTiles)");
+    constexpr int NWAVES = THREADS / 64;
+    constexpr int NG = (int)kGroupBatchSelect, NA = TWO ? NG / 2 : NG, NB = TWO ? 2 : 1;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    __shared__ uint64_t s_hist[NWAVES][NG][kSelectSlotCols];
+    select_group_zero<NG>(s_hist, NWAVES, t, THREADS);
+    PackedHist h[NG];
+    uint32_t c_rows[NG / 2];  // (not counted here: the fold adds zeros)
+    uint32_t want[NG], alive = 0;  // uniform: each group's bucket of the previous chunk in its low PC bits
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        c_rows[j >> 1] = 0;
+#pragma unroll
+        for (int i = 0; i < (1 << kSelectChunk) / 2; ++i) h[j].v[i] = 0;
+        const SelectState* st = select_group_state(g.workspace, (uint32_t)j);
+        want[j] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(st->prefix >> prev_low));
+        if (__builtin_amdgcn_readfirstlane((int)(st->found != 0))) alive |= 1u << j;
+    }
+    if (alive) {  // uniform; a batch without a found group leaves the candidates and the histograms alone
+        const int ptop = (int)prev_low + PC - 1, ntop = (int)prev_low - 1;
+        uint32_t since = 0;
+        const uint32_t n_idx = a.num_tiles;
+        for (uint32_t i = blockIdx.x; i < n_idx; i += gridDim.x) {
+            const uint64_t tile_word0 = (uint64_t)tile_at(a, i) * TILE_WORDS;
+            const bool whole = tile_word0 + TILE_WORDS <= a.n_words;
+#pragma unroll 1
+            for (int p = 0; p < PAIRS; ++p) {
+                const uint64_t pi = (tile_word0 >> 1) + (uint64_t)(p * THREADS + t);
+                const u64x2 c = reinterpret_cast<const u64x2*>(g.cand)[pi];
+                if (__ballot((c.x | c.y) != 0) == 0) continue;  // no candidate in the wave's 128 words
+                u64x2 ea[NA], eb[2], pw[PC], w[NC];
+                load_group_leaves<NA, TWO, THREADS>(q, whole, tile_word0, p, t, a.n_words, ea, eb);
+#pragma unroll
+                for (int s = 0; s < PC; ++s)
+                    pw[s] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(g.slices.s[ptop - s]) + pi);
+#pragma unroll
+                for (int s = 0; s < NC; ++s)
+                    w[s] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(g.slices.s[ntop - s]) + pi);
+                u64x2 keep = {0ull, 0ull};
+#pragma unroll
+                for (int x = 0; x < NA; ++x) {
+#pragma unroll
+                    for (int y = 0; y < NB; ++y) {
+                        const int j = NB * x + y;
+                        if (!((alive >> j) & 1u)) continue;  // uniform: the group has no such row
+                        u64x2 m = c & ea[x] & eb[y];
+#pragma unroll
+                        for (int s = 0; s < PC; ++s) {
+                            if ((want[j] >> (PC - 1 - s)) & 1u) m &= pw[s];
+                            else m &= ~pw[s];
+                        }
+                        keep |= m;
+                        if (__ballot((m.x | m.y) != 0) == 0) continue;
+                        select_hist_rec<NC, 0, 0>(w, m, (uint32_t)(__popcll(m.x) + __popcll(m.y)), h[j]);
+                    }
+                }
+                reinterpret_cast<u64x2*>(g.cand)[pi] = keep;
+            }
+            if (++since == kSelectFoldTiles) {  // uniform
+                select_group_fold<NG>(h, c_rows, s_hist[wave], lane);
+                since = 0;
+            }
+        }
+    }
+    select_group_fold<NG>(h, c_rows, s_hist[wave], lane);
+    select_group_publish<NG>(s_hist, NWAVES, g.workspace, t, THREADS);
+}
+
+// The column path's pass: x / valid as select_arrays_kernel reads them, the group columns as
+// aggregate_arrays_grouped_kernel's. Every row maps to its slot (group_slot_of); pass 0 counts the
+// slot's rows; a valid row whose key ^ 2^63 has the slot's prefix above bit shift + 4 adds one to the
+// slot's bucket of bits [shift, shift + 4) — per-(slot, bucket) LDS counters, CUBIT_AGG_MAX_GROUPS × 2^4 of
+// 64 bits (32 KB). Rows off their slot's prefix, and rows of a slot whose found is 0, are ignored.
+__global__ __launch_bounds__(256) void select_arrays_grouped_kernel(const int64_t* __restrict__ x,
+                                                                    const uint64_t* __restrict__ valid,
+                                                                    GroupColArgs gc, uint32_t n_groups,
+                                                                    const uint64_t* __restrict__ d_count,
+                                                                    uint64_t max_n, int type, uint32_t shift, int first,
+                                                                    int64_t* __restrict__ workspace) {
+    constexpr uint32_t NB = 1u << kSelectGroupArrayBits;
+    static_assert(NB + 1 == kSelectSlotCols, "a slot's buckets, then its rows");
+    __shared__ unsigned long long s_h[CUBIT_AGG_MAX_GROUPS][kSelectSlotCols];
+    __shared__ uint64_t s_prefix[CUBIT_AGG_MAX_GROUPS];
+    __shared__ uint32_t s_found[CUBIT_AGG_MAX_GROUPS];
+    const uint64_t hi_mask = first ? 0ull : ~0ull << (shift + kSelectGroupArrayBits);
+    for (uint32_t s = threadIdx.x; s < n_groups; s += blockDim.x) {
+#pragma unroll
+        for (uint32_t b = 0; b < kSelectSlotCols; ++b) s_h[s][b] = 0;
+        // (the first pass takes every valid row: the states are not set yet)
+        const SelectState* st = select_group_state(workspace, s);
+        s_prefix[s] = first ? 0ull : st->prefix & hi_mask;
+        s_found[s] = first || st->found ? 1u : 0u;
+    }
+    __syncthreads();
+    const uint64_t n = min(*d_count, max_n);
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int s1 = group_slot_of(gc, 0, i);
+        const int s2 = gc.n_cols > 1 ? group_slot_of(gc, 1, i) : 0;
+        if (s1 < 0 || s2 < 0) continue;
+        const uint32_t slot = (uint32_t)s1 * gc.n2 + (uint32_t)s2;
+        if (slot >= n_groups) continue;
+        if (first) atomicAdd(&s_h[slot][NB], 1ull);
+        if (!s_found[slot] || (valid && !((valid[i >> 6] >> (i & 63)) & 1ull))) continue;
+        const uint64_t off = (uint64_t)value_key(type, x[i]) ^ 0x8000000000000000ull;
+        if ((off & hi_mask) != s_prefix[slot]) continue;
+        atomicAdd(&s_h[slot][(uint32_t)(off >> shift) & (NB - 1)], 1ull);
+    }
+    __syncthreads();
+    const uint32_t cols = n_groups * kSelectSlotCols;
+    const unsigned long long* flat = &s_h[0][0];
+    for (uint32_t c = threadIdx.x; c < cols; c += blockDim.x) workspace[(uint64_t)cols * blockIdx.x + c] = (int64_t)flat[c];
+}
+
+// One workgroup after each pass of either path: sums the nblocks partials of n_slots · kSelectSlotCols
+// counters — thread t takes column t mod cols of every (1024 / cols)-th workgroup when the columns are
+// fewer than the threads, else every 1024-th column of every workgroup, so the loads spread as
+// select_step_kernel's — then one thread per slot applies select_step to the slot's state (`first`
+// also keeps the slot's rows), and `last` writes select_result to out + 6·group[slot] (q.group; the
+// slot itself with identity; kNoGroup: nothing). A slot without a row writes six zeros.
+__global__ __launch_bounds__(kSelectStepThreads) void select_step_grouped_kernel(
+    int64_t* __restrict__ workspace, int nblocks, uint32_t n_slots, uint32_t low, int first, int last, int mode, uint64_t k,
+    double quantile, int type, int64_t base, GroupAggArgs q, int identity, int64_t* __restrict__ out) {
+    constexpr uint32_t NB = 1u << kSelectChunk;
+    __shared__ uint64_t s_part[kSelectStepThreads];
+    __shared__ uint64_t s_counts[CUBIT_AGG_MAX_GROUPS * kSelectSlotCols];
+    const uint32_t lane = threadIdx.x, cols = n_slots * kSelectSlotCols;
+    if (cols < (uint32_t)kSelectStepThreads) {
+        const uint32_t stripes = (uint32_t)kSelectStepThreads / cols, j = lane % cols, s0 = lane / cols;
+        uint64_t sum = 0;
+        if (s0 < stripes)
+            for (uint32_t b = s0; b < (uint32_t)nblocks; b += stripes) sum += (uint64_t)workspace[(uint64_t)cols * b + j];
+        s_part[lane] = sum;
+        __syncthreads();
+        if (lane < cols) {
+            uint64_t c = 0;
+            for (uint32_t s = 0; s < stripes; ++s) c += s_part[s * cols + lane];
+            s_counts[lane] = c;
+        }
+    } else {
+        for (uint32_t j = lane; j < cols; j += (uint32_t)kSelectStepThreads) {
+            uint64_t sum = 0;
+            for (uint32_t b = 0; b < (uint32_t)nblocks; ++b) sum += (uint64_t)workspace[(uint64_t)cols * b + j];
+            s_counts[j] = sum;
+        }
+    }
+    __syncthreads();
+    if (lane < n_slots) {
+        const uint64_t* counts = s_counts + lane * kSelectSlotCols;
+        SelectState* st = select_group_state(workspace, lane);
+        SelectState state = *st;
+        select_step(&state, first != 0, mode, k, quantile, counts, NB, low);
+        *st = state;
+        uint64_t* rows = select_group_rows(workspace, lane);
+        if (first) *rows = counts[NB];
+        const uint32_t group = identity ? lane : q.group[lane < kGroupBatchSum ? lane : 0];
+        if (last && group != kNoGroup) {
+            int64_t r[6];
+            select_result(state, type, base, *rows, r);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) out[(uint64_t)group * 6 + i] = r[i];
+        }
     }
 }
 
@@ -5364,6 +5725,69 @@ hipError_t launch_select_arrays(const int64_t* x, const uint64_t* valid, const u
                            p == 0 ? 1 : 0, workspace);
         hipLaunchKernelGGL(select_step_kernel, dim3(1), dim3(kSelectStepThreads), 0, stream, workspace, (int)grid, 1u << kSelectArrayBits,
                            shift, p == 0 ? 1 : 0, p + 1 == passes ? 1 : 0, mode, k, q, type, INT64_MIN, out);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_slice_select_grouped(const EvalArgs& a, const SliceSelectArgs& g, const GroupAggArgs& q, int mode,
+                                       uint64_t k, double quantile, int type, int64_t base, int n_cus, int64_t* out,
+                                       hipStream_t stream, uint32_t* n_passes, hipEvent_t ev0, hipEvent_t ev1) {
+    constexpr uint32_t limit = kGroupBatchSelect;
+    if (g.n_slices > kMaxSlices || a.num_tiles == 0 || !g.workspace || !g.cand || q.n2 > 2 || q.n1 == 0 ||
+        q.n1 > (q.n2 ? limit / 2 : limit))
+        return hipErrorInvalidValue;
+    // one workgroup per CU: at the kernels' register count a CU holds one
+    const unsigned grid = slice_grid(a.num_tiles, n_cus, 1);
+    const bool two = q.n2 != 0;
+    const uint32_t bits = g.n_slices, passes = select_passes(bits, kSelectChunk);
+    if (n_passes) *n_passes = passes;
+    hipError_t e = dispatch_k0_form(a.prog, [&](auto kk, auto form) {
+        if (two)
+            hipExtLaunchKernelGGL((eval_slice_select_grouped<kk.value, form.value, true>), dim3(grid), dim3(512), 0, stream,
+                                  ev0, nullptr, 0, a, g, q);
+        else
+            hipExtLaunchKernelGGL((eval_slice_select_grouped<kk.value, form.value, false>), dim3(grid), dim3(512), 0, stream,
+                                  ev0, nullptr, 0, a, g, q);
+    });
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    for (uint32_t p = 0; p < passes; ++p) {
+        const uint32_t low = select_chunk_low(bits, kSelectChunk, p);
+        if (p > 0) {
+            const uint32_t pc = select_chunk_bits(bits, kSelectChunk, p - 1), plow = select_chunk_low(bits, kSelectChunk, p - 1);
+#define CUBIT_NARROW(PC)                                                                                              \
+    if (two) hipLaunchKernelGGL((slice_select_narrow_grouped<PC, true>), dim3(grid), dim3(512), 0, stream, a, g, q, plow); \
+    else hipLaunchKernelGGL((slice_select_narrow_grouped<PC, false>), dim3(grid), dim3(512), 0, stream, a, g, q, plow)
+            if (pc == 1) { CUBIT_NARROW(1); }
+            else if (pc == 2) { CUBIT_NARROW(2); }
+            else if (pc == 3) { CUBIT_NARROW(3); }
+            else { CUBIT_NARROW(4); }
+#undef CUBIT_NARROW
+        }
+        const bool last = p + 1 == passes;
+        hipExtLaunchKernelGGL(select_step_grouped_kernel, dim3(1), dim3(kSelectStepThreads), 0, stream, nullptr,
+                              last ? ev1 : nullptr, 0, g.workspace, (int)grid, limit, low, p == 0 ? 1 : 0, last ? 1 : 0, mode, k,
+                              quantile, type, base, q, 0, out);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_select_arrays_grouped(const int64_t* x, const uint64_t* valid, const GroupColArgs& gc, uint32_t n_groups,
+                                        const uint64_t* d_count, uint64_t max_n, int mode, uint64_t k, double quantile,
+                                        int type, int64_t* workspace, int64_t* out, hipStream_t stream, uint32_t* n_passes) {
+    if (n_groups == 0 || n_groups > CUBIT_AGG_MAX_GROUPS || !workspace) return hipErrorInvalidValue;
+    const unsigned grid =
+        (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((max_n + 2047) / 2048, select_group_col_grid(n_groups)));
+    constexpr uint32_t passes = 64 / kSelectGroupArrayBits;
+    if (n_passes) *n_passes = passes;
+    GroupAggArgs none{};
+    for (uint32_t p = 0; p < passes; ++p) {
+        const uint32_t shift = 64 - (p + 1) * kSelectGroupArrayBits;
+        hipLaunchKernelGGL(select_arrays_grouped_kernel, dim3(grid), dim3(256), 0, stream, x, valid, gc, n_groups, d_count,
+                           max_n, type, shift, p == 0 ? 1 : 0, workspace);
+        hipLaunchKernelGGL(select_step_grouped_kernel, dim3(1), dim3(kSelectStepThreads), 0, stream, workspace, (int)grid,
+                           n_groups, shift, p == 0 ? 1 : 0, p + 1 == passes ? 1 : 0, mode, k, quantile, type, INT64_MIN, none, 1,
+                           out);
     }
     return hipGetLastError();
 }

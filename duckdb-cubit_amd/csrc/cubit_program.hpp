@@ -539,6 +539,42 @@ inline bool select_from_slices(bool force_slices, bool force_column, bool usable
                             8.0 * (double)(64 / kSelectArrayBits));
 }
 
+// ---- selection by rank per group (cubit_table_select_grouped): the select above over the groups of
+// cubit_table_aggregate_grouped. The groups of one call are pairwise disjoint row sets, so one
+// candidate bitvector carries the radix selects of a whole batch of groups: a batch runs through all
+// its passes (each group narrowed by its own chosen bucket) before the next batch starts.
+constexpr uint32_t kGroupBatchSelect = 8;  // groups per launch (the resource table is in DESIGN.md §3)
+static_assert(kGroupBatchSelect <= kGroupBatchSum, "GroupAggArgs holds the batch");
+// bits per pass of the grouped array select: 2^4 buckets × CUBIT_AGG_MAX_GROUPS groups of 64-bit LDS counters
+constexpr uint32_t kSelectGroupArrayBits = 4;
+// the bits a live row costs the slice path, summed over the launches: the ungrouped select's, plus
+// the launch's group leaves in each of its passes. No batch (no group leaf): one launch without leaves.
+inline uint64_t select_grouped_slice_bits(const std::vector<GroupBatch>& bs, uint32_t bits, uint32_t k_leaves,
+                                          bool nullable) {
+    const uint32_t passes = select_passes(bits, kSelectChunk);
+    const uint32_t last = select_chunk_bits(bits, kSelectChunk, passes - 1);
+    const uint64_t per_row = k_leaves + (nullable ? 1u : 0u) + 1u + 2u * bits - last + 2u * (passes - 1);
+    if (bs.empty()) return per_row;
+    uint64_t sum = 0;
+    for (const GroupBatch& b : bs) sum += per_row + (uint64_t)(b.na + b.nb) * passes;
+    return sum;
+}
+// Which path cubit_table_select_grouped takes (path_from_slices; the value column and each group
+// column are probed: elem_bytes holds the value column's size, then each group column's):
+//   slices: slice_bits = select_grouped_slice_bits over the launches;
+//   column: the grouped aggregate's scan + probes, then the array passes, each reading the 8-byte
+//           probed value of every probed column: 64/kSelectGroupArrayBits passes with a group column,
+//           the ungrouped array select's 64/kSelectArrayBits with none.
+// The constants are derived from bytes alone and marked so. With no group leaf and one launch this is
+// select_from_slices.
+inline bool select_grouped_from_slices(bool force_slices, bool force_column, bool usable, uint64_t slice_bits,
+                                       uint32_t k_leaves, uint64_t live_rows, uint64_t rows, uint64_t est_rows,
+                                       const uint64_t* elem_bytes, uint32_t n_probed) {
+    const uint32_t array_passes = 64 / (n_probed > 1 ? kSelectGroupArrayBits : kSelectArrayBits);
+    return path_from_slices(force_slices, force_column, usable, slice_bits, k_leaves, live_rows, rows, est_rows, elem_bytes,
+                            n_probed, 8.0 * (double)array_passes * (double)n_probed);
+}
+
 // One past the last node of the subtree rooted at node i of a prefix-order node array, or -1 when
 // the array ends inside it. A negative child count reads as none.
 inline int filter_subtree_end(const cubit_filter_node* nodes, uint32_t n_nodes, uint32_t i) {

@@ -219,6 +219,12 @@ GPU_SIGNATURES = {
     "cubit_table_select": (C.c_int, [_P, _P, _U32, _P, C.c_int, C.c_int, _U64, C.c_double, _U32, _P]),
     "cubit_table_last_select": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(_U32)]),
     "cubit_bitslice_select": (C.c_int, [_P, _P, _U32, _P, _P, _U64, C.c_int, _I64, C.c_int, _U64, C.c_double, _P]),
+    "cubit_table_select_grouped": (C.c_int, [_P, _P, _U32, _P, C.c_int, _P, _U32, C.c_int, _U64, C.c_double, _U32, _P,
+                                             _U32]),
+    "cubit_table_last_select_grouped": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(_U32), C.POINTER(_U32),
+                                                  C.POINTER(_U32)]),
+    "cubit_bitslice_select_grouped": (C.c_int, [_P, _P, _U32, _P, _P, _P, _U32, _U64, C.c_int, _I64, C.c_int, _U64,
+                                                C.c_double, _P]),
     "cubit_table_top_n": (C.c_int, [_P, _P, _U32, _P, C.c_int, _U64, _U32, _P, _U64, _P, _P]),
     "cubit_table_column_data": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int)]),
     "cubit_table_set_inserts": (C.c_int, [_P, _P, _P, _P, _U64]),

@@ -894,6 +894,57 @@ class CubitTable:
         L.check(self.lib.cubit_table_last_grouped(self.handle, C.byref(fs), C.byref(ng), C.byref(nl)))
         return bool(fs.value), int(ng.value), int(nl.value)
 
+    def _select_by(self, col, by, mode, k, q, filter_set, residual, txn, path, zonemap) -> Dict[tuple, "Selected"]:
+        if path not in (None, "slices", "column"):
+            raise ValueError(f"path {path!r}")
+        flags = {None: 0, "slices": L.SELECT_FROM_SLICES, "column": L.SELECT_FROM_COLUMN}[path]
+        flags |= 0 if zonemap else L.SELECT_NO_ZONEMAP
+        groups = self.aggregate_groups(by)
+        cols, arr = self._group_cols(by)
+        plan = serialize(filter_set, residual)
+        nodes = to_ctypes(plan.nodes)
+        ng = len(groups)
+        out = self.ctx.alloc(max(ng, 1) * 48)
+        try:
+            L.check(self.lib.cubit_table_select_grouped(self.handle, nodes, len(plan.nodes),
+                                                        C.byref(txn) if txn is not None else None, col, arr, len(cols),
+                                                        mode, int(k), float(q), flags, C.c_void_p(out.addr), ng))
+            self.ctx.check()
+            res = out.download(np.int64, ng * 6).reshape(ng, 6) if ng else np.zeros((0, 6), dtype=np.int64)
+        finally:
+            out.free()
+        result = {}
+        for key, row in zip(groups, res):
+            v, found, below, equal, cv, cr = (int(x) for x in row)
+            if cr == 0:
+                continue
+            result[key] = Selected(v if found else None, bool(found), below, equal, cv, cr)
+        return result
+
+    def quantile_by(self, col: int, q: float, by, filter_set: Optional[TableFilterSet] = None,
+                    residual: Optional[Residual] = None, txn: Optional[L.Txn] = None, path: Optional[str] = None,
+                    zonemap: bool = True) -> Dict[tuple, "Selected"]:
+        """SELECT by…, quantile_disc(col, q) WHERE <filter> GROUP BY by… → {key tuple: Selected}, the keys
+        as aggregate_groups gives them (None: the NULL group) and each Selected as quantile()'s. Groups
+        without a qualifying row are left out. path and zonemap as aggregate()'s."""
+        return self._select_by(col, by, L.SELECT_QUANTILE, 0, q, filter_set, residual, txn, path, zonemap)
+
+    def kth_by(self, col: int, k: int, by, desc: bool = False, filter_set: Optional[TableFilterSet] = None,
+               residual: Optional[Residual] = None, txn: Optional[L.Txn] = None, path: Optional[str] = None,
+               zonemap: bool = True) -> Dict[tuple, "Selected"]:
+        """kth() per group of by…: the same rank k in every group → {key tuple: Selected} (found False in
+        a group with k >= count_valid, its counts still given)."""
+        return self._select_by(col, by, L.SELECT_RANK_DESC if desc else L.SELECT_RANK, k, 0.0, filter_set, residual,
+                               txn, path, zonemap)
+
+    def last_select_grouped(self):
+        """(whether the last quantile_by() / kth_by() read the bit slices, its group count, its batches
+        of groups — 0 on the column path — and the passes per batch)."""
+        fs, ng, nl, npass = C.c_int(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        L.check(self.lib.cubit_table_last_select_grouped(self.handle, C.byref(fs), C.byref(ng), C.byref(nl),
+                                                         C.byref(npass)))
+        return bool(fs.value), int(ng.value), int(nl.value), int(npass.value)
+
     def last_sum_packed(self) -> bool:
         v = C.c_int()
         L.check(self.lib.cubit_table_last_sum_packed(self.handle, C.byref(v)))

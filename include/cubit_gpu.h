@@ -978,6 +978,50 @@ int cubit_table_last_select(cubit_table *t, int *from_slices, uint32_t *n_passes
 int cubit_bitslice_select(cubit_ctx *ctx, const uint64_t *const *d_slices, uint32_t n_slices,
                           const uint64_t *d_validity, const uint64_t *d_filter, uint64_t n_rows, int type,
                           int64_t base, int mode, uint64_t k, double q, int64_t *d_out);
+/* Selection by rank per group: SELECT g, quantile_disc(col, q) ... GROUP BY g, the per-group k-th
+ * value likewise. The groups and their numbering are exactly cubit_table_aggregate_groups' (one or two
+ * group columns, each with an EQUALITY index over every distinct value; a NULL slot last; slots made
+ * by update values included; g = i1 * n2 + i2; at most CUBIT_AGG_MAX_GROUPS), and the refusals are
+ * cubit_table_aggregate_grouped's: CUBIT_ERR_UNSUPPORTED names the column, cap_groups below the group
+ * count is CUBIT_ERR_CAPACITY, n_group_cols = 0 is CUBIT_ERR_INVALID (cubit_table_select is that call).
+ *   For group g, d_out + 6 * g (device, cap_groups * 6 int64) holds the six slots of cubit_table_select
+ * over the group's qualifying rows, with its value form, NULL handling and type rules (FLOAT / DOUBLE /
+ * UINT64 / dictionary columns work: a select needs only the order). mode, k and q are
+ * cubit_table_select's and the same for every group: with CUBIT_SELECT_RANK / _RANK_DESC a group with
+ * count_valid <= k has found = 0 and its counts still written; with CUBIT_SELECT_QUANTILE each group's
+ * rank comes from its own count_valid, computed on the device. A group without a qualifying row has six
+ * zeros; so has every group of an empty partition or under a filter that folds to FALSE. The result
+ * is ready on the context's stream with no host round trip.
+ *   flags: CUBIT_SELECT_FROM_SLICES | _FROM_COLUMN | _NO_ZONEMAP (any other bit, or both force flags, is
+ * CUBIT_ERR_INVALID). From the slices (usable as cubit_table_aggregate_grouped's slice path: a non-empty
+ * bit-sliced index on col, cubit_table_use_sliced on, no update record of col or of a group column
+ * visible to txn; FROM_SLICES without that is CUBIT_ERR_INVALID): the groups of a call are pairwise
+ * disjoint, so one scratch candidate bitvector carries the radix selects of a whole batch of up to 8
+ * groups. Pass 0 evaluates the filter program, forms each group's rows as F AND E1 AND E2 in registers,
+ * writes the union of the groups' candidates and histograms the first chunk per group; each later
+ * pass narrows the candidates by each group's own chosen bucket and histograms the next chunk; one
+ * workgroup after each pass steps every group's state. A batch runs through all its passes before
+ * the next starts. Per batch about (K [+ 1] + 1 + 2b - 4 + 2 * (passes - 1) + leaves * passes) / 8
+ * bytes per row of the evaluated zones. A slot that exists only because of an update value has no
+ * bitvector and no rows on this path. From the column: scan into scratch, probe col and each group
+ * column with validity (visible MVCC updates applied), then one radix select for all groups over the
+ * probed values, 4 bits per pass. cubit_table_last_select_grouped tells which ran, the group count, the
+ * batches (0 on the column path) and the passes per batch (the column path: its 16 array passes); any
+ * of its pointers may be NULL. cubit_table_last_select stays the ungrouped call's. */
+int cubit_table_select_grouped(cubit_table *t, const cubit_filter_node *nodes, uint32_t n_nodes, const cubit_txn *txn,
+                               int col, const int *group_cols, uint32_t n_group_cols, int mode, uint64_t k, double q,
+                               uint32_t flags, int64_t *d_out, uint32_t cap_groups);
+int cubit_table_last_select_grouped(cubit_table *t, int *from_slices, uint32_t *n_groups, uint32_t *n_launches,
+                                    uint32_t *n_passes);
+/* The grouped slice path's kernels on a caller's slices: arguments as cubit_bitslice_select's, plus
+ * n_groups (1 ... CUBIT_AGG_MAX_GROUPS) group bitvectors d_groups, each cubit_padded_words(n_rows) words,
+ * 16-byte aligned. d_out + 6 * g = the six slots over the rows of group g. The group bitvectors must be
+ * PAIRWISE DISJOINT: that is the caller's contract, and overlapping groups give unspecified numbers.
+ * A row in no group belongs to no result. */
+int cubit_bitslice_select_grouped(cubit_ctx *ctx, const uint64_t *const *d_slices, uint32_t n_slices,
+                                  const uint64_t *d_validity, const uint64_t *d_filter,
+                                  const uint64_t *const *d_groups, uint32_t n_groups, uint64_t n_rows, int type,
+                                  int64_t base, int mode, uint64_t k, double q, int64_t *d_out);
 /* ... WHERE <filter> ORDER BY col [DESC], rowid LIMIT k: the global row ids of the first k qualifying
  * non-NULL rows into d_rowids, in ascending row-id order — every row strictly before the threshold
  * value (the value of rank k - 1), then the lowest row ids among the rows equal to it until k.
