@@ -67,7 +67,11 @@ int fail(int code, const char* fmt, ...) {
 
 struct cubit_ctx {
     int device = 0;
+    // n_cus: the compute units the launchers size their grids by — the device's (device_cus), or
+    // fewer under cubit_ctx_set_compute_units, never more
     int n_cus = 256;
+    int device_cus = 256;
+    LaunchShape last_grid;  // cubit_ctx_last_grid: the last tile-walking launch's workgroups and tiles
     hipStream_t stream = nullptr;
     bool timing = false;
     // one (start, stop) event pair per timed filter-kernel launch since the last reset
@@ -398,6 +402,11 @@ int run_eval(cubit_ctx* ctx, const EvalProgram& prog, uint64_t n_rows, int64_t r
                            ? CUBIT_DECODE_PREFIXED
                            : decode_kernel_for(prog.n_leaves, a.num_tiles, grid, kernel, a.live != nullptr, ctx->n_cus,
                                                prefixed);
+    // the look-back kernel, its prefixed form and the row-list kernel launch one workgroup per tile
+    const bool per_tile =
+        from_list || ctx->last_decode == CUBIT_DECODE_LOOKBACK || ctx->last_decode == CUBIT_DECODE_PREFIXED;
+    const uint32_t walked = from_list ? la.tiles : a.num_tiles;
+    ctx->last_grid = LaunchShape{per_tile ? walked : grid, walked};
     ctx->last_tiles = (uint32_t)tiles;
     ctx->last_tile_rows = decode_tile_words() * 64;
     if (order_pass)
@@ -440,7 +449,7 @@ int cubit_ctx_create(int device, cubit_ctx** out) {
     ctx->device = device;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-        ctx->n_cus = prop.multiProcessorCount;
+        ctx->n_cus = ctx->device_cus = prop.multiProcessorCount;
     if (hipMalloc(&ctx->partials, 2 * kSumBlocks * sizeof(int64_t)) != hipSuccess ||
         hipMalloc(&ctx->agg, kAggWorkspace * sizeof(int64_t)) != hipSuccess ||
         hipMalloc(&ctx->ticket, kTicketWords * sizeof(uint64_t)) != hipSuccess ||
@@ -531,6 +540,32 @@ int cubit_ctx_set_lookback_spins(cubit_ctx* ctx, uint32_t spins) {
     if (!ctx) return fail(CUBIT_ERR_INVALID, "null context");
     CUBIT_LOCK(ctx);
     ctx->lookback_spins = spins;
+    return CUBIT_OK;
+}
+
+int cubit_ctx_set_compute_units(cubit_ctx* ctx, int n) {
+    if (!ctx) return fail(CUBIT_ERR_INVALID, "null context");
+    CUBIT_LOCK(ctx);
+    // lower only: a count above the device's could size a grid past what is co-resident
+    if (n < 0 || n > ctx->device_cus)
+        return fail(CUBIT_ERR_INVALID, "compute units %d (the device has %d)", n, ctx->device_cus);
+    ctx->n_cus = n == 0 ? ctx->device_cus : n;
+    return CUBIT_OK;
+}
+
+int cubit_ctx_compute_units(cubit_ctx* ctx, int* device, int* in_use) {
+    if (!ctx || !device || !in_use) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(ctx);
+    *device = ctx->device_cus;
+    *in_use = ctx->n_cus;
+    return CUBIT_OK;
+}
+
+int cubit_ctx_last_grid(cubit_ctx* ctx, uint32_t* workgroups, uint32_t* tiles) {
+    if (!ctx || !workgroups || !tiles) return fail(CUBIT_ERR_INVALID, "null argument");
+    CUBIT_LOCK(ctx);
+    *workgroups = ctx->last_grid.workgroups;
+    *tiles = ctx->last_grid.tiles;
     return CUBIT_OK;
 }
 
@@ -868,7 +903,8 @@ int cubit_bitslice_aggregate(cubit_ctx* ctx, const uint64_t* const* d_slices, ui
     if (int rc = tile_eval_args(ctx, prog, n_rows, 0, kAggTileWords, {}, a)) return rc;
     hipEvent_t e0, e1;
     if (int rc = timing_events(ctx, e0, e1)) return rc;
-    HIP_CHECK(launch_eval_slice_aggregate(a, g, ops, type, base, ctx->n_cus, d_out, ctx->stream, e0, e1));
+    HIP_CHECK(launch_eval_slice_aggregate(a, g, ops, type, base,
+                                          ctx->n_cus, &ctx->last_grid, d_out, ctx->stream, e0, e1));
     return CUBIT_OK;
 }
 
@@ -913,7 +949,8 @@ int cubit_bitslice_sum_product(cubit_ctx* ctx, const uint64_t* const* d_a_slices
     if (int rc = tile_eval_args(ctx, prog, n_rows, 0, kAggTileWords, {}, a)) return rc;
     hipEvent_t e0, e1;
     if (int rc = timing_events(ctx, e0, e1)) return rc;
-    HIP_CHECK(launch_eval_slice_sum_product(a, g, a_outer ? base_a : base_b, a_outer ? base_b : base_a, ctx->n_cus, d_out,
+    HIP_CHECK(launch_eval_slice_sum_product(a, g, a_outer ? base_a : base_b, a_outer ? base_b : base_a,
+                                            ctx->n_cus, &ctx->last_grid, d_out,
                                             4, nullptr, ctx->stream, e0, e1));
     return CUBIT_OK;
 }
@@ -957,7 +994,8 @@ int cubit_bitslice_select(cubit_ctx* ctx, const uint64_t* const* d_slices, uint3
     if (int rc = tile_eval_args(ctx, prog, n_rows, 0, kAggTileWords, {}, a)) return rc;
     hipEvent_t e0, e1;
     if (int rc = timing_events(ctx, e0, e1)) return rc;
-    HIP_CHECK(launch_slice_select(a, g, mode, k, q, type, base, ctx->n_cus, d_out, ctx->stream, nullptr, e0, e1));
+    HIP_CHECK(launch_slice_select(a, g, mode, k, q, type, base,
+                                  ctx->n_cus, &ctx->last_grid, d_out, ctx->stream, nullptr, e0, e1));
     return CUBIT_OK;
 }
 
@@ -1011,7 +1049,8 @@ int cubit_bitslice_select_grouped(cubit_ctx* ctx, const uint64_t* const* d_slice
         }
         hipEvent_t e0, e1;
         if (int rc = timing_events(ctx, e0, e1)) return rc;
-        HIP_CHECK(launch_slice_select_grouped(a, g, qa, mode, k, q, type, base, ctx->n_cus, d_out, ctx->stream, nullptr, e0, e1));
+        HIP_CHECK(launch_slice_select_grouped(a, g, qa, mode, k, q, type, base,
+                                              ctx->n_cus, &ctx->last_grid, d_out, ctx->stream, nullptr, e0, e1));
     }
     return CUBIT_OK;
 }
@@ -5561,8 +5600,9 @@ extern "C" int cubit_table_sum_product(cubit_table* t, const cubit_filter_node* 
             if (int rc = tile_eval_args(ctx, em.prog, t->n_rows, t->row_base, kAggTileWords, live, a)) return rc;
             hipEvent_t e0, e1;
             if (int rc = timing_events(ctx, e0, e1)) return rc;
-            HIP_CHECK(launch_eval_slice_sum_product(a, g, po.sx->vmin, pi.sx->vmin, ctx->n_cus, d_out, 2, count, ctx->stream,
-                                                    e0, e1));
+            HIP_CHECK(launch_eval_slice_sum_product(a, g, po.sx->vmin, pi.sx->vmin,
+                                                    ctx->n_cus, &ctx->last_grid, d_out, 2,
+                                                    count, ctx->stream, e0, e1));
             t->last_sum_slices = true;
             t->last_sum_launches = 1;
             t->last_sliced += 2;
@@ -5613,6 +5653,7 @@ extern "C" int cubit_table_sum_product(cubit_table* t, const cubit_filter_node* 
     }
     const unsigned grid = std::min<unsigned>(a.num_tiles, sum_product_grid((unsigned)ctx->n_cus));
     HIP_CHECK(launch_eval_sum_product(a, sa, std::max(grid, 1u), d_out, ctx->stream));
+    ctx->last_grid = LaunchShape{std::max(grid, 1u), a.num_tiles};
     return CUBIT_OK;
 }
 
@@ -5656,7 +5697,8 @@ extern "C" int cubit_table_aggregate(cubit_table* t, const cubit_filter_node* no
         if (int rc = tile_eval_args(ctx, p.em.prog, t->n_rows, t->row_base, kAggTileWords, p.live, a)) return rc;
         hipEvent_t e0, e1;
         if (int rc = timing_events(ctx, e0, e1)) return rc;
-        HIP_CHECK(launch_eval_slice_aggregate(a, g, ops & kOps, c.type, p.sx->vmin, ctx->n_cus, d_out, ctx->stream, e0, e1));
+        HIP_CHECK(launch_eval_slice_aggregate(a, g, ops & kOps, c.type, p.sx->vmin,
+                                              ctx->n_cus, &ctx->last_grid, d_out, ctx->stream, e0, e1));
         t->last_agg_slices = true;
         t->last_sliced++;
         return CUBIT_OK;
@@ -5724,7 +5766,8 @@ extern "C" int cubit_table_select(cubit_table* t, const cubit_filter_node* nodes
         if (int rc = tile_eval_args(ctx, p.em.prog, t->n_rows, t->row_base, kAggTileWords, p.live, a)) return rc;
         hipEvent_t e0, e1;
         if (int rc = timing_events(ctx, e0, e1)) return rc;
-        HIP_CHECK(launch_slice_select(a, g, mode, k, q, c.type, p.sx->vmin, ctx->n_cus, d_out, ctx->stream,
+        HIP_CHECK(launch_slice_select(a, g, mode, k, q, c.type, p.sx->vmin,
+                                      ctx->n_cus, &ctx->last_grid, d_out, ctx->stream,
                                       &t->last_sel_passes, e0, e1));
         t->last_sel_slices = true;
         t->last_sliced++;
@@ -6043,7 +6086,8 @@ extern "C" int cubit_table_aggregate_grouped(cubit_table* t, const cubit_filter_
             fill_group_batch(b, la, lb, two, swapped, n2, q);
             hipEvent_t e0, e1;
             if (int rc = timing_events(ctx, e0, e1)) return rc;
-            HIP_CHECK(launch_eval_slice_aggregate_grouped(a, g, q, ops & kOps, c.type, p.sx->vmin, ctx->n_cus, d_out,
+            HIP_CHECK(launch_eval_slice_aggregate_grouped(a, g, q, ops & kOps, c.type, p.sx->vmin,
+                                                          ctx->n_cus, &ctx->last_grid, d_out,
                                                           ctx->stream, e0, e1));
             t->last_grouped_launches++;
         }
@@ -6141,7 +6185,8 @@ extern "C" int cubit_table_select_grouped(cubit_table* t, const cubit_filter_nod
             fill_group_batch(b, la, lb, two, swapped, n2, qa);
             hipEvent_t e0, e1;
             if (int rc = timing_events(ctx, e0, e1)) return rc;
-            HIP_CHECK(launch_slice_select_grouped(a, g, qa, mode, k, q, c.type, p.sx->vmin, ctx->n_cus, d_out, ctx->stream,
+            HIP_CHECK(launch_slice_select_grouped(a, g, qa, mode, k, q, c.type, p.sx->vmin,
+                                                  ctx->n_cus, &ctx->last_grid, d_out, ctx->stream,
                                                   &t->last_gsel_passes, e0, e1));
             t->last_gsel_launches++;
         }
@@ -6249,7 +6294,8 @@ extern "C" int cubit_table_sum_product_grouped(cubit_table* t, const cubit_filte
             fill_group_batch(b, la, lb, two, swapped, n2, q);
             hipEvent_t e0, e1;
             if (int rc = timing_events(ctx, e0, e1)) return rc;
-            HIP_CHECK(launch_eval_slice_sum_product_grouped(a, g, q, so.vmin, si.vmin, ctx->n_cus, d_out, ctx->stream, e0, e1));
+            HIP_CHECK(launch_eval_slice_sum_product_grouped(a, g, q, so.vmin, si.vmin,
+                                                            ctx->n_cus, &ctx->last_grid, d_out, ctx->stream, e0, e1));
             t->last_sum_launches++;
         }
         t->last_sum_slices = true;

@@ -142,6 +142,13 @@ constexpr uint32_t kTicketGroups = 8;
 constexpr uint32_t kTicketWords = kTicketStride * (kTicketGroups + 2);
 
 // launchers (cubit_kernels.hip); all asynchronous on `stream`
+// what a tile-walking launch used (cubit_ctx_last_grid): the workgroups of its persistent grid and
+// the tiles they walked between them. The slice launchers fill `shape` (optional) from the grid they
+// launch, for a select from pass 0's
+struct LaunchShape {
+    uint32_t workgroups = 0;
+    uint32_t tiles = 0;
+};
 uint64_t decode_tile_words();  // words per eval_decode_tiles tile
 uint64_t count_tile_words(uint32_t n_leaves);  // words per eval_count_kernel tile
 int decode_block_threads();
@@ -242,7 +249,8 @@ constexpr uint64_t kAggTileWords = 2048;
 // launcher; a.num_tiles tiles of kAggTileWords words (a.live: the zones to evaluate); ops =
 // CUBIT_AGG_SUM | _MIN | _MAX; type / base: the column's type and the slices' base key
 hipError_t launch_eval_slice_aggregate(EvalArgs a, const SliceAggArgs& g, uint32_t ops, int type, int64_t base,
-                                       int n_cus, int64_t* out, hipStream_t stream, hipEvent_t ev0 = nullptr,
+                                       int n_cus, LaunchShape* shape,
+                                       int64_t* out, hipStream_t stream, hipEvent_t ev0 = nullptr,
                                        hipEvent_t ev1 = nullptr);
 // the same result from x[i] (the probed values as the ABI carries them, 0 at NULL rows) and valid
 // (bit i, null = all valid), i < min(*d_count, max_n)
@@ -266,7 +274,8 @@ struct SliceProductArgs {
 };
 // a as launch_eval_slice_aggregate's (a.count is set by the launcher)
 hipError_t launch_eval_slice_sum_product(EvalArgs a, const SliceProductArgs& g, int64_t base_outer, int64_t base_inner,
-                                         int n_cus, int64_t* out, int out_slots, uint64_t* count_out, hipStream_t stream,
+                                         int n_cus, LaunchShape* shape,
+                                         int64_t* out, int out_slots, uint64_t* count_out, hipStream_t stream,
                                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // Selection by rank (cubit_table_select): a radix select over the column's slices (eval_slice_select,
 // slice_select_narrow: kSelectChunk slices per pass) or over probed values (select_arrays_kernel:
@@ -298,7 +307,8 @@ struct SliceSelectArgs {
 // a as launch_eval_slice_aggregate's (a.count is set by the launcher); mode / k / q: CUBIT_SELECT_*, the
 // rank, the quantile; *n_passes (optional) = the passes over the slices
 hipError_t launch_slice_select(EvalArgs a, const SliceSelectArgs& g, int mode, uint64_t k, double q, int type,
-                               int64_t base, int n_cus, int64_t* out, hipStream_t stream, uint32_t* n_passes = nullptr,
+                               int64_t base, int n_cus, LaunchShape* shape,
+                               int64_t* out, hipStream_t stream, uint32_t* n_passes = nullptr,
                                hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // the same result from x[i] / valid as launch_aggregate_arrays takes them
 hipError_t launch_select_arrays(const int64_t* x, const uint64_t* valid, const uint64_t* d_count, uint64_t max_n,
@@ -335,7 +345,8 @@ struct GroupAggArgs {
 // ops holds MIN or MAX) with one group column, half that with two. out: the whole result, 6 int64
 // per group.
 hipError_t launch_eval_slice_aggregate_grouped(const EvalArgs& a, const SliceAggArgs& g, const GroupAggArgs& q,
-                                               uint32_t ops, int type, int64_t base, int n_cus, int64_t* out,
+                                               uint32_t ops, int type, int64_t base, int n_cus, LaunchShape* shape,
+                                               int64_t* out,
                                                hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // The column path's reduction per group: x / xvalid as launch_aggregate_arrays', and per group column
 // its probed values, their validity words, its type, the ascending keys of its non-NULL slots
@@ -362,7 +373,8 @@ constexpr int kProductGroupPartial = 8;
 static_assert((uint64_t)kProductGroupPartial * kProductGroupBatch * kAggMaxGrid <= kGroupWorkspace, "the slice path's partials fit");
 constexpr unsigned kProductColGrid = (unsigned)(kGroupWorkspace / ((uint64_t)kProductGroupPartial * CUBIT_AGG_MAX_GROUPS));
 hipError_t launch_eval_slice_sum_product_grouped(const EvalArgs& a, const SliceProductArgs& g, const GroupAggArgs& q,
-                                                 int64_t base_outer, int64_t base_inner, int n_cus, int64_t* out,
+                                                 int64_t base_outer, int64_t base_inner, int n_cus, LaunchShape* shape,
+                                                 int64_t* out,
                                                  hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // the column path's reduction: xa / xb the probed operands (0 at NULL rows) with their validity words
 // (null: all valid), gc as launch_aggregate_arrays_grouped's
@@ -406,7 +418,8 @@ __host__ __device__ inline uint64_t* select_group_rows(int64_t* workspace, uint3
 // launch_eval_slice_aggregate_grouped's with q.n1 ≤ kGroupBatchSelect (half that with two group
 // columns; q.partials is not used). The same k / q for every group.
 hipError_t launch_slice_select_grouped(const EvalArgs& a, const SliceSelectArgs& g, const GroupAggArgs& q, int mode,
-                                       uint64_t k, double quantile, int type, int64_t base, int n_cus, int64_t* out,
+                                       uint64_t k, double quantile, int type, int64_t base,
+                                       int n_cus, LaunchShape* shape, int64_t* out,
                                        hipStream_t stream, uint32_t* n_passes = nullptr, hipEvent_t ev0 = nullptr,
                                        hipEvent_t ev1 = nullptr);
 // the same result for every group from x / valid and gc as launch_aggregate_arrays_grouped takes them

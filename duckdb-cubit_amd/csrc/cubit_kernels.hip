@@ -5633,10 +5633,12 @@ void launch_slice_aggregate_kf(const EvalArgs& a, const SliceAggArgs& g, uint32_
 }
 
 hipError_t launch_eval_slice_aggregate(EvalArgs a, const SliceAggArgs& g, uint32_t ops, int type, int64_t base,
-                                       int n_cus, int64_t* out, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+                                       int n_cus, LaunchShape* shape,
+                                       int64_t* out, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
     if (g.n_slices > kMaxSlices || a.num_tiles == 0 || !g.workspace || !a.ticket) return hipErrorInvalidValue;
     a.count = agg_count_slot(g.workspace);
     const unsigned grid = slice_grid(a.num_tiles, n_cus, 2);  // two workgroups per CU, as the fused sum's
+    if (shape) *shape = LaunchShape{grid, a.num_tiles};
     hipError_t e = dispatch_k0_form(a.prog, [&](auto k, auto form) {
         launch_slice_aggregate_kf<k.value, form.value>(a, g, ops, grid, stream, ev0, ev1);
     });
@@ -5648,13 +5650,15 @@ hipError_t launch_eval_slice_aggregate(EvalArgs a, const SliceAggArgs& g, uint32
 }
 
 hipError_t launch_eval_slice_sum_product(EvalArgs a, const SliceProductArgs& g, int64_t base_outer, int64_t base_inner,
-                                         int n_cus, int64_t* out, int out_slots, uint64_t* count_out, hipStream_t stream,
+                                         int n_cus, LaunchShape* shape,
+                                         int64_t* out, int out_slots, uint64_t* count_out, hipStream_t stream,
                                          hipEvent_t ev0, hipEvent_t ev1) {
     if (g.n_outer > kMaxSlices || g.n_inner > g.n_outer || a.num_tiles == 0 || !g.workspace || !a.ticket)
         return hipErrorInvalidValue;
     a.count = agg_count_slot(g.workspace);
     // two workgroups per CU, as the aggregate's; the workspace holds kProductMaxGrid partials
     const unsigned grid = std::min(slice_grid(a.num_tiles, n_cus, 2), kProductMaxGrid);
+    if (shape) *shape = LaunchShape{grid, a.num_tiles};
     hipError_t e = dispatch_k0_form(a.prog, [&](auto k, auto form) {
         hipExtLaunchKernelGGL((eval_slice_sum_product<k.value, form.value>), dim3(grid), dim3(512), 0, stream, ev0, ev1, 0,
                               a, g);
@@ -5677,11 +5681,13 @@ hipError_t launch_aggregate_arrays(const int64_t* x, const uint64_t* valid, cons
 }
 
 hipError_t launch_slice_select(EvalArgs a, const SliceSelectArgs& g, int mode, uint64_t k, double q, int type,
-                               int64_t base, int n_cus, int64_t* out, hipStream_t stream, uint32_t* n_passes,
+                               int64_t base, int n_cus, LaunchShape* shape,
+                               int64_t* out, hipStream_t stream, uint32_t* n_passes,
                                hipEvent_t ev0, hipEvent_t ev1) {
     if (g.n_slices > kMaxSlices || a.num_tiles == 0 || !g.workspace || !g.cand || !a.ticket) return hipErrorInvalidValue;
     a.count = select_count_slot(g.workspace);
     const unsigned grid = slice_grid(a.num_tiles, n_cus, 2);  // as the aggregate's
+    if (shape) *shape = LaunchShape{grid, a.num_tiles};
     const uint32_t bits = g.n_slices, passes = select_passes(bits, kSelectChunk);
     if (n_passes) *n_passes = passes;
     hipError_t e = dispatch_k0_form(a.prog, [&](auto kk, auto form) {
@@ -5730,7 +5736,8 @@ hipError_t launch_select_arrays(const int64_t* x, const uint64_t* valid, const u
 }
 
 hipError_t launch_slice_select_grouped(const EvalArgs& a, const SliceSelectArgs& g, const GroupAggArgs& q, int mode,
-                                       uint64_t k, double quantile, int type, int64_t base, int n_cus, int64_t* out,
+                                       uint64_t k, double quantile, int type, int64_t base,
+                                       int n_cus, LaunchShape* shape, int64_t* out,
                                        hipStream_t stream, uint32_t* n_passes, hipEvent_t ev0, hipEvent_t ev1) {
     constexpr uint32_t limit = kGroupBatchSelect;
     if (g.n_slices > kMaxSlices || a.num_tiles == 0 || !g.workspace || !g.cand || q.n2 > 2 || q.n1 == 0 ||
@@ -5738,6 +5745,7 @@ hipError_t launch_slice_select_grouped(const EvalArgs& a, const SliceSelectArgs&
         return hipErrorInvalidValue;
     // one workgroup per CU: at the kernels' register count a CU holds one
     const unsigned grid = slice_grid(a.num_tiles, n_cus, 1);
+    if (shape) *shape = LaunchShape{grid, a.num_tiles};
     const bool two = q.n2 != 0;
     const uint32_t bits = g.n_slices, passes = select_passes(bits, kSelectChunk);
     if (n_passes) *n_passes = passes;
@@ -5815,7 +5823,8 @@ void launch_slice_aggregate_grouped_kf(const EvalArgs& a, const SliceAggArgs& g,
 }
 
 hipError_t launch_eval_slice_aggregate_grouped(const EvalArgs& a, const SliceAggArgs& g, const GroupAggArgs& q,
-                                               uint32_t ops, int type, int64_t base, int n_cus, int64_t* out,
+                                               uint32_t ops, int type, int64_t base, int n_cus, LaunchShape* shape,
+                                               int64_t* out,
                                                hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
     const bool minmax = (ops & (kAggMin | kAggMax)) != 0;
     const uint32_t limit = minmax ? kGroupBatchMinMax : kGroupBatchSum;
@@ -5823,6 +5832,7 @@ hipError_t launch_eval_slice_aggregate_grouped(const EvalArgs& a, const SliceAgg
         q.n1 > (q.n2 ? limit / 2 : limit))
         return hipErrorInvalidValue;
     const unsigned grid = slice_grid(a.num_tiles, n_cus, 1);  // one workgroup per CU at the kernel's register count
+    if (shape) *shape = LaunchShape{grid, a.num_tiles};
     hipError_t e = dispatch_k0_form(a.prog, [&](auto k, auto form) {
         launch_slice_aggregate_grouped_kf<k.value, form.value>(a, g, q, minmax, grid, stream, ev0, ev1);
     });
@@ -5849,13 +5859,15 @@ hipError_t launch_aggregate_arrays_grouped(const int64_t* x, const uint64_t* val
 }
 
 hipError_t launch_eval_slice_sum_product_grouped(const EvalArgs& a, const SliceProductArgs& g, const GroupAggArgs& q,
-                                                 int64_t base_outer, int64_t base_inner, int n_cus, int64_t* out,
+                                                 int64_t base_outer, int64_t base_inner, int n_cus, LaunchShape* shape,
+                                                 int64_t* out,
                                                  hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
     constexpr uint32_t limit = kProductGroupBatch;
     if (g.n_outer > kMaxSlices || g.n_inner > g.n_outer || a.num_tiles == 0 || !q.partials || q.n2 > 2 || q.n1 == 0 ||
         q.n1 > (q.n2 ? limit / 2 : limit))
         return hipErrorInvalidValue;
     const unsigned grid = slice_grid(a.num_tiles, n_cus, 1);  // one workgroup per CU at the kernel's register count
+    if (shape) *shape = LaunchShape{grid, a.num_tiles};
     const bool two = q.n2 != 0;
     hipError_t e = dispatch_k0_form(a.prog, [&](auto k, auto form) {
         if (two)

@@ -39,6 +39,25 @@ class Context:
         (0 = library default); a small value forces the expiry path."""
         L.check(self.lib.cubit_ctx_set_lookback_spins(self.handle, spins))
 
+    def set_compute_units(self, n: int) -> None:
+        """Size the launchers' grids as on a device of `n` compute units (1 … the device's count;
+        0 = the device's own). It only lowers: small tables then run several tiles per workgroup,
+        as large ones do. Results are identical under any setting."""
+        L.check(self.lib.cubit_ctx_set_compute_units(self.handle, int(n)))
+
+    def compute_units(self) -> Tuple[int, int]:
+        """(the device's compute units, the count the launchers use)."""
+        dev, use = C.c_int(), C.c_int()
+        L.check(self.lib.cubit_ctx_compute_units(self.handle, C.byref(dev), C.byref(use)))
+        return int(dev.value), int(use.value)
+
+    def last_grid(self) -> Tuple[int, int]:
+        """(workgroups, tiles) of the last tile-walking launch (slice kernels, fused sum, decode),
+        as its launcher set them; a multi-pass select reports its first pass."""
+        wg, tiles = C.c_uint32(), C.c_uint32()
+        L.check(self.lib.cubit_ctx_last_grid(self.handle, C.byref(wg), C.byref(tiles)))
+        return int(wg.value), int(tiles.value)
+
     def last_decode_kernel(self) -> int:
         k = C.c_int()
         L.check(self.lib.cubit_ctx_last_decode_kernel(self.handle, C.byref(k)))

@@ -251,6 +251,19 @@ int cubit_ctx_set_decode_kernel(cubit_ctx *ctx, int kernel);
  * launch — no workgroup waits without bound and the count is always exact — and a small limit
  * forces it (tests). */
 int cubit_ctx_set_lookback_spins(cubit_ctx *ctx, uint32_t spins);
+/* The compute units the context's launchers size their persistent grids by: 0 = the device's own
+ * count (the default), 1 … the device's count = that many; anything else is CUBIT_ERR_INVALID. The
+ * setting only ever lowers a count, so a grid only shrinks and the look-back kernel is admitted to
+ * no more tiles than before. With a small count a table of a few tiles runs the loops of a table of
+ * hundreds — several tiles per workgroup, uneven shares (tests). Results are identical under any
+ * setting. cubit_ctx_compute_units reads the device's count and the one in use. */
+int cubit_ctx_set_compute_units(cubit_ctx *ctx, int n);
+int cubit_ctx_compute_units(cubit_ctx *ctx, int *device, int *in_use);
+/* The workgroups the context's last tile-walking launch used and the tiles they walked between them
+ * (the live tiles, under a zonemap skip), as its launcher set them: the slice-answered aggregates,
+ * selects (the first pass) and sums of products, the fused filter+SUM, and the decode. Zeros before
+ * the first such launch; a call answered without a launch leaves the earlier values. */
+int cubit_ctx_last_grid(cubit_ctx *ctx, uint32_t *workgroups, uint32_t *tiles);
 /* The kernel the context's last decode launched (CUBIT_DECODE_PAIRS, _RUNS, _LOOKBACK or _PREFIXED; 0 when
  * the partition had no row and nothing was launched). */
 int cubit_ctx_last_decode_kernel(cubit_ctx *ctx, int *kernel);
